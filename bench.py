@@ -7,9 +7,15 @@
 
 One process per GPU (RANK/LOCAL_RANK/WORLD_SIZE from the env), per-GPU batch 32 (weak scaling), gradients
 all-reduced over RCCL by slowfast_amd.data_parallel.GradReducer overlapped with backward.  Rank 0 prints ONE
-JSON line.  `value` = clips/s of the whole job with the clips already resident in HBM.  After the timed
-region one more step is run with HIP events around every libsfamd launch (slowfast_amd.profiler) to report the
-dominant kernel against its roofline, and (N=1 only) the CPU oracle is timed on a bounded sample.
+JSON line.  `value` = clips/s of the whole job with the clips already resident in HBM; `ms_per_step` = the
+milliseconds of one timed step.  A plain run does nothing else: set-up, warm-up, the K timed steps, the result line.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; inputs and weights are
+seeded, so two builds can be compared output for output).
+
+`--full` adds what the headline figure does not need: after the timed region one more step is run with HIP events
+around every libsfamd launch (slowfast_amd.profiler) to report the dominant kernel against its roofline, (N=1 only)
+the CPU oracle is timed on a bounded sample, the default preset appends MViTv2-S (`secondary`) and the other GPU
+configurations of BASELINE.json (`others`), and N > 1 reports the `multi_gpu` attribution block.
 """
 import argparse
 import json
@@ -111,11 +117,20 @@ def parse():
                     help="torch.optim fused SGD / AdamW + separate unscale / norm / clip passes (round-1 step glue) instead of "
                          "slowfast_amd.optim.FlatOptimizer (one norm pass + one fused update, device-side dynamic loss scale)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the second model of BASELINE.json's metric (MViTv2-S) that the default run appends as `secondary`")
+                    help="skip the second model of BASELINE.json's metric (MViTv2-S) that the --full run appends as `secondary`")
     ap.add_argument("--no-others", action="store_true",
                     help="skip the remaining GPU configurations of BASELINE.json (X3D-M batch 64, SlowFast-R101 + Nonlocal AVA batch 16) "
-                         "that the default run appends as `others` (--no-secondary skips them too)")
+                         "that the --full run appends as `others` (--no-secondary skips them too)")
     ap.add_argument("--master-port", type=int, default=0, help="(self-spawned multi-GPU runs) rendezvous port, 0 = pick a free one")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel roofline step, the CPU oracle "
+                         "baseline, the second model (`secondary`), the other GPU configurations (`others`) and, at N > 1, the "
+                         "`multi_gpu` attribution block.  Without it the run sets up, warms up, times --steps steps and prints "
+                         "the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, logits, gradient norm, a fixed "
+                         "seeded sample of the updated parameters, the BatchNorm running statistics) as DIR/<name>.npy: float32, the "
+                         "sample's indices float64")
     return ap.parse_args()
 
 
@@ -219,7 +234,39 @@ def spawn_ranks(a):
     return subprocess.call(cmd, env=dict(os.environ))
 
 
-def run_preset(a, preset, batch, steps, warmup, rank, local, world, dev, kernel_profile, cpu_base):
+DUMP_PARAM_SAMPLE = 1 << 21      # parameters written by --dump-outputs: at most 2 M values (+ float64 indices: 24 MB)
+
+
+def dump_outputs(directory, train_step, model, loss):
+    """--dump-outputs: the arrays a caller of the timed step receives after its last iteration -- the loss, the logits, the
+    global gradient norm, the updated parameters (all of them, or a fixed seeded sample of at most DUMP_PARAM_SAMPLE values
+    of their concatenation in model.parameters() order, with its indices) and the BatchNorm running statistics -- as float32
+    .npy files.  Copied to the host right after the timed region, before anything else touches the model."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    out = {"loss": loss.detach().float().reshape(1)}
+    logits = train_step.logits
+    if logits is not None:
+        out["logits"] = logits.detach().float()
+    if torch.is_tensor(train_step.grad_norm):
+        out["grad_norm"] = train_step.grad_norm.detach().float().reshape(1)
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    if flat.numel() > DUMP_PARAM_SAMPLE:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(flat.numel(), generator=g)[:DUMP_PARAM_SAMPLE].sort().values
+        out["params_sample"] = flat[idx.to(flat.device)]
+        out["params_sample_index"] = idx.double()       # exact in float64 up to 2^53
+    else:
+        out["params"] = flat
+    bufs = [b.detach().reshape(-1).float() for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var"))]
+    if bufs:
+        out["bn_running_stats"] = torch.cat(bufs)
+    for name, t in out.items():
+        arr = t.cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), arr if arr.dtype == np.float64 else arr.astype(np.float32))
+
+
+def run_preset(a, preset, batch, steps, warmup, rank, local, world, dev, kernel_profile, cpu_base, dump_dir=None):
     """Builds the model of `preset`, times `steps` training steps, returns the result object (rank 0) or None."""
     import slowfast_amd as sa
     from slowfast_amd import lib as sflib
@@ -324,14 +371,16 @@ def run_preset(a, preset, batch, steps, warmup, rank, local, world, dev, kernel_
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.detach())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, train_step, model, loss)
 
     # N > 1: what a scaling efficiency below 0.9 would have to be attributed to.  `overlap_log` = collectives
     # still in flight when the LAST backward segment starts (per timed iteration); `one_stream` = the same binary with the
     # pathway / branch streams off (engine.run_pathways / run_branches), i.e. without RCCL's kernels sharing the chip with a
     # two-queue backward.
     multi = None
-    # (SF_BENCH_ATTRIB=1 runs the same block on one GPU: the only way to exercise it on a one-GPU box)
-    if (world > 1 or os.environ.get("SF_BENCH_ATTRIB") == "1") and not a.dry_run_cpu:
+    # (--full only; SF_BENCH_ATTRIB=1 runs the same block on one GPU: the only way to exercise it on a one-GPU box)
+    if a.full and (world > 1 or os.environ.get("SF_BENCH_ATTRIB") == "1") and not a.dry_run_cpu:
         from slowfast_amd import engine as _eng
         multi = {"overlap_log": list(train_step.overlap_log)[-steps:], "segments": len(getattr(train_step, "_seg_params", []) or []),
                  "buckets": len(reducer.buckets)}
@@ -484,7 +533,9 @@ def main():
             dist.init_process_group(backend="gloo")
         assert get_lib().backend == "hostsim", "--dry-run-cpu runs on the host simulator (SFAMD_LIBRARY)"
         a.no_graph, a.no_secondary, a.no_kernel_profile, a.no_cpu_baseline = True, True, True, True
-    else:
+    elif not a.full:        # a plain run measures the headline figure only
+        a.no_secondary, a.no_kernel_profile, a.no_cpu_baseline = True, True, True
+    if not a.dry_run_cpu:
         torch.cuda.set_device(local)
         dev = torch.device("cuda", local)
         if world > 1:
@@ -492,8 +543,9 @@ def main():
         assert get_lib().backend == "gfx950", "bench.py measures the HIP library only"
 
     out = run_preset(a, a.preset, a.batch, a.steps, a.warmup, rank, local, world, dev,
-                     kernel_profile=not a.no_kernel_profile, cpu_base=(world == 1 and not a.no_cpu_baseline))
-    # BASELINE.json's metric names two models: the default single-GPU run appends the second one (MViTv2-S 16x224^2, batch
+                     kernel_profile=not a.no_kernel_profile, cpu_base=(world == 1 and not a.no_cpu_baseline),
+                     dump_dir=a.dump_outputs)
+    # BASELINE.json's metric names two models: the --full single-GPU run appends the second one (MViTv2-S 16x224^2, batch
     # 32) measured the same way in the same process, so that the driver's line carries both
     if a.preset == "SLOWFAST_8x8_R50" and world == 1 and not a.no_secondary and a.batch == 32:
         a.cpu_baseline_timeout = min(a.cpu_baseline_timeout, 150.0)     # the second model's CPU sample is bounded harder

@@ -7,7 +7,7 @@ to fp32 round-off, and store the reference's numbers (logits, loss, grad-norm, p
 updated BN running statistics checksums).  The fixtures let the GPU box (which has no /root/reference)
 check the oracle -- and through it the HIP engine -- against the reference's own outputs.
 
-    python -m oracle.make_golden
+    python -m oracle.make_golden [case ...]        (reference_contract: tests/golden/reference_contract.json)
 """
 import json
 import os
@@ -302,10 +302,110 @@ def eval_forward(sd, cfg, inputs):
     return fwd(sd, cfg, inputs, training=False)
 
 
+# tests/test_oracle.py: the reference models whose state_dict keys / shapes the drop-ins must expose, the reference YAMLs whose
+# values the built-in presets must carry, and the frames the data oracle is checked on -- recorded from the reference into
+# tests/golden/reference_contract.json, so that the tests hold wherever the reference tree is absent
+_SUB_BN = ["BN.NORM_TYPE", "sub_batchnorm", "BN.NUM_SPLITS", 2]
+STATE_DICT_CASES = [("configs/Kinetics/SLOWFAST_8x8_R50.yaml", "SLOWFAST_8x8_R50", []),
+                    ("configs/Kinetics/C2D_8x8_R50.yaml", "C2D_8x8_R50", []),
+                    ("configs/Kinetics/SLOW_8x8_R50.yaml", "SLOW_8x8_R50", []),
+                    ("configs/Kinetics/I3D_8x8_R50.yaml", "I3D_8x8_R50", []),
+                    ("configs/Kinetics/MVITv2_S_16x4.yaml", "MVITv2_S_16x4", []),
+                    ("configs/Kinetics/MVIT_B_16x4_CONV.yaml", "MVIT_B_16x4_CONV", []),
+                    ("configs/masked_ssl/k400_VIT_B_16x4_FT.yaml", "k400_VIT_B_16x4_FT", []),
+                    ("configs/Kinetics/MVITv2_S_16x4.yaml", "MVITv2_S_16x4", ["MVIT.CLS_EMBED_ON", False, "MVIT.SEPARATE_QKV", True]),
+                    ("configs/Kinetics/MVIT_B_16x4_CONV.yaml", "MVIT_B_16x4_CONV", ["MVIT.POOL_FIRST", True, "MVIT.CLS_EMBED_ON", False]),
+                    ("configs/Kinetics/REV_MVIT_B_16x4_CONV.yaml", "REV_MVIT_B_16x4_CONV", ["MVIT.CLS_EMBED_ON", False]),
+                    ("configs/Kinetics/X3D_M.yaml", "X3D_M", []),
+                    ("configs/Kinetics/C2D_NLN_8x8_R50.yaml", "C2D_NLN_8x8_R50", []),
+                    ("configs/Kinetics/SLOWFAST_NLN_8x8_R50.yaml", "SLOWFAST_NLN_8x8_R50", []),
+                    ("configs/Kinetics/SLOWFAST_8x8_R50.yaml", "SLOWFAST_8x8_R50", _SUB_BN),
+                    ("configs/Kinetics/X3D_M.yaml", "X3D_M", _SUB_BN),
+                    ("configs/Kinetics/SLOW_8x8_R50.yaml", "SLOW_8x8_R50", ["BN.NORM_TYPE", "sync_batchnorm", "BN.NUM_SYNC_DEVICES", 1])]
+# reference YAML -> the config sections the preset tests compare (plus CFG_DATA_KEYS of DATA for every one)
+_RESNET_SECTIONS, _MVIT_SECTIONS = ("RESNET", "SLOWFAST", "NONLOCAL", "MODEL", "BN"), ("MVIT",)
+CFG_YAMLS = {**{f"configs/Kinetics/{n}.yaml": _RESNET_SECTIONS for n in ("SLOWFAST_8x8_R50", "C2D_8x8_R50", "SLOW_8x8_R50",
+                                                                         "I3D_8x8_R50", "C2D_NLN_8x8_R50", "SLOWFAST_NLN_8x8_R50")},
+             **{y: _MVIT_SECTIONS for y in ("configs/Kinetics/MVITv2_S_16x4.yaml", "configs/Kinetics/MVIT_B_16x4_CONV.yaml",
+                                            "configs/Kinetics/REV_MVIT_B_16x4_CONV.yaml", "configs/masked_ssl/k400_VIT_B_16x4_FT.yaml")}}
+CFG_DATA_KEYS = ("NUM_FRAMES", "SAMPLING_RATE", "TRAIN_CROP_SIZE", "TEST_CROP_SIZE", "INPUT_CHANNEL_NUM")
+DATA_CASES = (("slowfast", False), ("slowfast", True), ("c2d", False))
+
+
+def state_dict_case_key(yaml_rel, opts):
+    return yaml_rel + " " + json.dumps(opts)
+
+
+def plain(v):
+    """A config value as JSON holds it (CfgNode -> dict, tuple -> list)."""
+    if isinstance(v, dict):
+        return {k: plain(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [plain(x) for x in v]
+    return v
+
+
+def data_case(arch, reverse):
+    """The preset and the seeded uint8 frames (2 clips x 8 x 6 x 10 x 3) of one data-oracle case."""
+    import slowfast_amd as sa
+    cfg = sa.get_preset("SLOWFAST_8x8_R50" if arch == "slowfast" else "C2D_8x8_R50",
+                        ["DATA.MEAN", [0.45, 0.40, 0.35], "DATA.STD", [0.225, 0.25, 0.2], "DATA.REVERSE_INPUT_CHANNEL", reverse])
+    g = torch.Generator().manual_seed(1)
+    frames = torch.randint(0, 256, (2, 8, 6, 10, 3), generator=g, dtype=torch.int64).to(torch.uint8)
+    return cfg, frames
+
+
+def state_dict_digest(sd):
+    """Number of entries + sha256 over the (key, shape) list of a state_dict, in order."""
+    import hashlib
+    entries = [[k, list(v.shape)] for k, v in sd.items()]
+    return {"entries": len(entries), "sha256": hashlib.sha256(json.dumps(entries).encode()).hexdigest()}
+
+
+def tensor_digest(t):
+    """Shape + sha256 of the contiguous float32 bytes: equal digests == torch.equal."""
+    import hashlib
+    t = t.detach().to(torch.float32).contiguous()
+    return {"shape": list(t.shape), "sha256": hashlib.sha256(t.numpy().tobytes()).hexdigest()}
+
+
+def reference_contract():
+    """The record tests/golden/reference_contract.json holds, computed from the reference tree."""
+    import re
+    rec = {"state_dict": {}, "cfg": {}, "data": {}}
+    for yaml_rel, _preset, opts in STATE_DICT_CASES:
+        sd = refshim.reference_model(refshim.reference_cfg(yaml_rel, ["NUM_GPUS", 0] + opts)).state_dict()
+        rec["state_dict"][state_dict_case_key(yaml_rel, opts)] = state_dict_digest(sd)
+    for yaml_rel, sections in CFG_YAMLS.items():
+        ref = refshim.reference_cfg(yaml_rel)
+        c = {sec: plain(ref[sec]) for sec in sections}
+        c["DATA"] = {k: plain(ref.DATA[k]) for k in CFG_DATA_KEYS}
+        rec["cfg"][yaml_rel] = c
+    # slowfast/datasets/utils.py imports decoders / logging the data path does not need: execute only the two pure functions
+    src = open(os.path.join(refshim.REFERENCE_ROOT, "slowfast", "datasets", "utils.py")).read()
+    ns = {}
+    for fn in ("pack_pathway_output", "tensor_normalize"):
+        m = re.search(r"^def " + fn + r"\(.*?(?=^def |\Z)", src, re.S | re.M)
+        exec("import torch\n" + m.group(0), ns)
+    for arch, reverse in DATA_CASES:
+        cfg, frames = data_case(arch, reverse)
+        rec["data"][f"{arch}_reverse{int(reverse)}"] = [
+            [tensor_digest(r) for r in ns["pack_pathway_output"](
+                cfg, ns["tensor_normalize"](frames[n], cfg.DATA.MEAN, cfg.DATA.STD).permute(3, 0, 1, 2))]
+            for n in range(frames.shape[0])]
+    return rec
+
+
 def main():
     out_dir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(out_dir, exist_ok=True)
-    for name in (sys.argv[1:] or list(CASES) + list(EVAL_CASES)):
+    for name in (sys.argv[1:] or list(CASES) + list(EVAL_CASES) + ["reference_contract"]):
+        if name == "reference_contract":
+            rec = reference_contract()
+            with open(os.path.join(out_dir, name + ".json"), "w") as f:      # one line per case
+                f.write("{\n" + ",\n".join(f" {json.dumps(part)}: {{\n" + ",\n".join(
+                    f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in rec[part].items()) + "\n }" for part in rec) + "\n}\n")
+            continue
         rec = run_eval_case(name) if name in EVAL_CASES else run_case(name)
         with open(os.path.join(out_dir, name + ".json"), "w") as f:
             json.dump(rec, f)
