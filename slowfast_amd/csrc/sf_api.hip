@@ -7,7 +7,6 @@
 #include "sf_wgrad2.h"
 #include "sf_pool.h"
 #include "sf_dwconv.h"
-#include "sf_dwtile.h"
 #include "sf_dwsweep.h"
 #include "sf_dwtemporal.h"
 #include "sf_tokens.h"
@@ -44,7 +43,7 @@ static inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
 
 // Environment switches, two classes (47 getenv sites, many per launch, each an untested product configuration):
 //   test_hook(name, default)  dispatch thresholds the TEST SUITE lowers so that small shapes reach a kernel (SF_IGEMM2_MINK ...),
-//                             kernel selectors its parity cases flip (SF_DW_TILED ...) and SF_TRACE: read in every build;
+//                             kernel selectors its parity cases flip (SF_DW_SWEEP ...) and SF_TRACE: read in every build;
 //   tune_knob(name, default)  A/B knobs whose optimum was measured (block targets, occupancy caps, variant selectors; the
 //                             evidence is under profiles/): COMPILE-TIME constants in the product build, overridable only in
 //                             -DSF_DIAG builds (libsfamd_diag.so, tools/ sweeps).
@@ -1587,116 +1586,37 @@ static void dw_block_plan(DwParams& p, DwBlockIdx& bi, const sf_dw_desc* d, bool
         else hipLaunchKernelGGL((KERNEL<1, 1, SF_DW_SMALL_W, float>), grid, dim3(SF_THREADS), 0, s, p, bi);             \
     } while (0)
 // ------------------------------------------------------------------------------------------------
-// LDS-tiled plane sweep (sf_dwtile.h) for the 3x3x3 / padding 1 / stride (1, s, s) depthwise convolutions of the MViT pooling
-// path, forward and data gradient.  Taken when the geometry fits (32-channel chunks inside one weight group, no BatchNorm
-// statistics epilogue); SF_DW_TILED=0 keeps the W-blocked stencils (A/B runs).  mode 0: forward, 1: data gradient.
-static bool dwtile_plan(const sf_dw_desc* d, int mode, DwTileParams& p, int& np) {
-    // SF_DW_TILED: 0 = never, 1 (default) = stride-1 geometries (where it measured faster: profiles/r4/r4_v5_dwtile_ab.txt), 2 = also
-    // the stride-2 forward and the zero-upsampled stride-2 data gradient
-    const char* lv = getenv("SF_DW_TILED");        // read per call (tests switch it mid-process)
-    const int lvl = lv ? atoi(lv) : 1;
-    if (lvl == 0 || (lvl == 1 && d->sH != 1)) return false;
-    if (d->kT != 3 || d->kH != 3 || d->kW != 3 || d->pT != 1 || d->pH != 1 || d->pW != 1) return false;
-    if (d->sT != 1 || d->sH != d->sW || (d->sH != 1 && d->sH != 2)) return false;
-    if (d->Cw % SF_DWT_CC != 0 || d->C % SF_DWT_CC != 0 || d->To != d->Ti) return false;
-    memset(&p, 0, sizeof(p));
-    p.N = d->N; p.C = d->C; p.Cw = d->Cw; p.Cwreal = d->Cwreal ? d->Cwreal : d->Cw; p.cls = d->cls ? 1 : 0; p.T = d->Ti;
-    if (mode == 0) {
-        p.Hs = d->Hi; p.Ws = d->Wi; p.Hd = d->Ho; p.Wd = d->Wo; p.Hg = d->Hi; p.Wg = d->Wi; p.s = d->sH;
-    } else {
-        p.Hs = d->Ho; p.Ws = d->Wo; p.Hd = d->Hi; p.Wd = d->Wi; p.Hg = d->Hi; p.Wg = d->Wi; p.s = 1; p.flip = 1;
-        p.ups = d->sH == 2 ? 1 : 0;
-    }
-    p.CT = p.Wg + 2;
-    p.nchunks = d->C / SF_DWT_CC;
-    double best = 0.0;
-    int best_th = 0;
-    const char* e = getenv("SF_DWT_TH");            // tests force a row-tile height (read per call)
-    const int force_th = e ? atoi(e) : 0;
-    for (int th = p.Hd < 64 ? p.Hd : 64; th >= 1; --th) {
-        if (force_th > 0 && th != (force_th < p.Hd ? force_th : p.Hd)) continue;
-        const int rt = th * p.s + 2;
-        if ((int64_t)rt * p.CT * SF_DWT_PP > SF_DWT_PLANE || (int64_t)rt * p.CT * SF_DWT_G > SF_THREADS * SF_DWT_VPT) continue;
-        const int P = th * p.Wd, npk = cdiv(P, SF_DWT_PT);
-        if (npk > SF_DWT_NPMAX) continue;
-        const int tiles = cdiv(p.Hd, th);
-        const int npt = npk == 3 ? 4 : npk;                           // compiled for 1, 2, 4 positions per thread
-        const double eff = (double)p.Hd * p.Wd / ((double)tiles * npt * SF_DWT_PT);
-        const double halo = (double)(th * p.s) / rt;
-        const double blocks = (double)d->N * tiles * p.nchunks;
-        const double bal = blocks >= 768 ? 1.0 : blocks / 768.0;
-        const double score = eff * halo * bal;
-        if (score > best) { best = score; best_th = th; }
-    }
-    if (!best_th) return false;
-    p.TH = best_th; p.RT = best_th * p.s + 2;
-    p.tiles_h = cdiv(p.Hd, best_th);
-    np = cdiv(best_th * p.Wd, SF_DWT_PT);
-    if (np == 3) np = 4;
-    p.fdCT = make_fastdiv(p.CT); p.fdWd = make_fastdiv(p.Wd); p.fdG = make_fastdiv(SF_DWT_G);
-    const int64_t per_n_src = ((int64_t)p.T * p.Hs * p.Ws + p.cls), per_n_dst = ((int64_t)p.T * p.Hd * p.Wd + p.cls);
-    if (per_n_src * (mode == 0 ? d->ldx : d->ldy) >= (1ll << 31) || per_n_dst * (mode == 0 ? d->ldy : d->ldx) >= (1ll << 31)) return false;
-    return true;
-}
-static void dwtile_launch(DwTileParams& p, int np, hipStream_t s) {
-    const dim3 grid((unsigned)(p.N * p.tiles_h * p.nchunks));
-    static const bool trace = test_hook("SF_TRACE", 0) != 0;
-    if (trace) fprintf(stderr, "[sfamd] dwtile: N=%d C=%d T=%d %dx%d -> %dx%d s=%d ups=%d TH=%d tiles=%d NP=%d blocks=%u\n", p.N, p.C, p.T,
-                       p.Hs, p.Ws, p.Hd, p.Wd, p.s, p.ups, p.TH, p.tiles_h, np, grid.x);
-    if (np == 1) hipLaunchKernelGGL(sf_dwtile_kernel<1>, grid, dim3(SF_THREADS), 0, s, p);
-    else if (np == 2) hipLaunchKernelGGL(sf_dwtile_kernel<2>, grid, dim3(SF_THREADS), 0, s, p);
-    else hipLaunchKernelGGL(sf_dwtile_kernel<4>, grid, dim3(SF_THREADS), 0, s, p);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Ring-buffered plane sweep with the channels on the lanes (sf_dwsweep.h, round 6): every 3x3x3 / padding 1 / stride (1, s, s),
-// s = 1 | 2 depthwise convolution (MViT pooling, X3D channelwise), forward / data gradient / weight gradient.  SF_DW_SWEEP=0 keeps
-// the older kernels (A/B runs, read per call).  dir: 0 forward, 1 data gradient, 2 weight gradient.
+// Plane sweeps (sf_dwsweep.h, round 6) of the 3x3x3 / padding 1 / stride (1, s, s) depthwise convolutions (MViT pooling, X3D
+// channelwise).  SF_DW_SWEEP=0 keeps the stencils (tests, read per call).
 static bool dwsweep_shape_ok(const sf_dw_desc* d) {
     if (d->kT != 3 || d->kH != 3 || d->kW != 3 || d->pT != 1 || d->pH != 1 || d->pW != 1) return false;
     if (d->sT != 1 || d->sH != d->sW || (d->sH != 1 && d->sH != 2) || d->To != d->Ti) return false;
     return d->C % 8 == 0 && d->Cw % 8 == 0;
 }
 static int64_t dwsweep_max_rows(const sf_dw_desc* d) { return (int64_t)d->N * d->Ho * 4; }
-static bool dwsweep_plan(const sf_dw_desc* d, int dir, DwSweepParams& p, int& kmode, int& ks) {
-    const char* lv = getenv("SF_DW_SWEEP");
-    if (lv && atoi(lv) == 0) return false;
-    if (!dwsweep_shape_ok(d)) return false;
+// Stride-2 data gradient on sf_dwsweep_kernel<1, 2, .>: the iterated space is dy (a lane writes the 2 x 2 block of dx above each
+// position), the staged tile is dy with a one-row / one-column halo.  SF_DWS_TH / SF_DWS_TW / SF_DWS_NSEG force a tiling (tests).
+static bool dwsweep_plan(const sf_dw_desc* d, DwSweepParams& p) {
+    if (test_hook("SF_DW_SWEEP", 1) == 0) return false;
+    if (!dwsweep_shape_ok(d) || d->sH != 2) return false;
     memset(&p, 0, sizeof(p));
     p.N = d->N; p.C = d->C; p.Cw = d->Cw; p.Cwreal = d->Cwreal ? d->Cwreal : d->Cw; p.cls = d->cls ? 1 : 0; p.T = d->Ti;
     p.nchunks = cdiv(d->C, 32);
-    const int s = d->sH;
-    int LS;                                             // rows of the staged tile between the rows of neighbouring lanes
-    if (dir == 0) { kmode = 0; ks = s; p.Ha = d->Hi; p.Wa = d->Wi; p.Hd = d->Ho; p.Wd = d->Wo; p.Hit = d->Ho; p.Wit = d->Wo; LS = s; }
-    else if (dir == 1 && s == 1) { kmode = 0; ks = 1; p.flip = 1; p.Ha = d->Ho; p.Wa = d->Wo; p.Hd = d->Hi; p.Wd = d->Wi; p.Hit = d->Hi; p.Wit = d->Wi; LS = 1; }
-    else if (dir == 1) { kmode = 1; ks = 2; p.Ha = d->Ho; p.Wa = d->Wo; p.Hd = d->Hi; p.Wd = d->Wi; p.Hit = d->Ho; p.Wit = d->Wo; LS = 1; }
-    else { kmode = 2; ks = s; p.Ha = d->Hi; p.Wa = d->Wi; p.Hb = d->Ho; p.Wb = d->Wo; p.Hit = d->Ho; p.Wit = d->Wo; LS = s; }
-    const int es = kmode == 1 ? 1 : ks;                 // staged positions per iterated position and axis
-    const int halo = kmode == 1 ? 1 : 2;
-    auto env_int = [](const char* n) { const char* e = getenv(n); return e ? atoi(e) : 0; };
-    const int f_th = env_int("SF_DWS_TH"), f_tw = env_int("SF_DWS_TW"), f_seg = env_int("SF_DWS_NSEG");     // tests / tuning
+    p.Ha = d->Ho; p.Wa = d->Wo; p.Hd = d->Hi; p.Wd = d->Wi; p.Hit = d->Ho; p.Wit = d->Wo;
+    const int f_th = test_hook("SF_DWS_TH", 0), f_tw = test_hook("SF_DWS_TW", 0), f_seg = test_hook("SF_DWS_NSEG", 0);
     double best = 0.0;
     for (int kw = 1; kw <= 16; ++kw) {
         const int tw = cdiv(p.Wit, kw);
         if (kw > 1 && tw == cdiv(p.Wit, kw - 1)) continue;
         if (f_tw > 0 && tw != (f_tw < p.Wit ? f_tw : p.Wit)) continue;
-        const int ca = (tw - 1) * es + 1 + halo;
+        const int ca = tw + 1;
         int rp = ca * 64;
-        if (LS == 1) { if (rp % 128 == 0) rp += 64; } else rp += 32;
+        if (rp % 128 == 0) rp += 64;
         for (int th = p.Hit < 32 ? p.Hit : 32; th >= 1; --th) {
             if (f_th > 0 && th != (f_th < p.Hit ? f_th : p.Hit)) continue;
-            const int ra = (th - 1) * es + 1 + halo;
+            const int ra = th + 1;
             const int slotb = roundup(ra * rp, 1024);
-            if (slotb > SF_DWS_MAXVPT * 4096) continue;
-            int lds = SF_DWS_NR * slotb, rpb = 0, slotbB = 0;
-            if (kmode == 2) {
-                rpb = tw * 64;
-                if (rpb % 128 == 0) rpb += 64;
-                slotbB = roundup(th * rpb, 1024);
-                if (slotbB > SF_DWS_MAXVPTB * 4096) continue;
-                lds += SF_DWS_NRB * slotbB;
-            }
-            if (lds > SF_DWS_LDS) continue;
+            if (slotb > SF_DWS_MAXVPT * 4096 || SF_DWS_NR * slotb > SF_DWS_LDS) continue;
             const int tiles_h = cdiv(p.Hit, th), tiles_w = cdiv(p.Wit, tw);
             if ((int64_t)p.N * tiles_h * tiles_w > dwsweep_max_rows(d)) continue;
             const int ngrp = cdiv(th, 8);
@@ -1709,7 +1629,7 @@ static bool dwsweep_plan(const sf_dw_desc* d, int dir, DwSweepParams& p, int& km
                 const double wave_cols = (double)cdiv(ntask, 4) * (sl + 0.5);
                 const double useful = (double)p.Hit * p.Wit / ((double)tiles_h * tiles_w);        // outputs of an average tile
                 const double valu_eff = useful / (wave_cols * 4.0 * 8.0);
-                const double stage_eff = (double)(th * es) * (tw * es) / ((double)ra * ca);        // halo re-reads (L2 -> LDS)
+                const double stage_eff = (double)th * tw / ((double)ra * ca);                      // halo re-reads (L2 -> LDS)
                 const double sweep = (double)p.T * wave_cols;
                 const double startup = sweep / (sweep + 10.0);                                      // weights + ring fill per workgroup
                 const double blocks = (double)p.N * tiles_h * tiles_w * p.nchunks;
@@ -1719,22 +1639,19 @@ static bool dwsweep_plan(const sf_dw_desc* d, int dir, DwSweepParams& p, int& km
                     best = score;
                     p.TH = th; p.TW = tw; p.tiles_h = tiles_h; p.tiles_w = tiles_w;
                     p.RA = ra; p.CA = ca; p.RP = rp; p.slotb = slotb; p.vpt = cdiv(slotb, 4096);
-                    p.RB = th; p.CBt = tw; p.RPB = rpb; p.slotbB = slotbB; p.vptB = slotbB ? cdiv(slotbB, 4096) : 0;
                     p.ngrp = ngrp; p.nseg = nseg; p.SL = sl;
                 }
             }
         }
     }
     if (best <= 0.0) return false;
-    p.fdRP = make_fastdiv(p.RP); p.fdRPB = make_fastdiv(p.RPB ? p.RPB : 1); p.fdSeg = make_fastdiv(p.nseg);
+    p.fdRP = make_fastdiv(p.RP); p.fdSeg = make_fastdiv(p.nseg);
     const int64_t per_n_a = (int64_t)p.T * p.Ha * p.Wa + p.cls;
-    const int lda = dir == 1 ? d->ldy : d->ldx;
-    if ((int64_t)p.Ha * p.Wa * lda >= (1ll << 31) || per_n_a * lda >= (1ll << 40)) return false;
-    if (kmode == 2 && (int64_t)p.Hb * p.Wb * d->ldy >= (1ll << 31)) return false;
+    if ((int64_t)p.Ha * p.Wa * d->ldy >= (1ll << 31) || per_n_a * d->ldy >= (1ll << 40)) return false;
     return true;
 }
 // Rotating-accumulator form of the sweep (sf_dwsweep.h: sf_dwrot_kernel): forward, stride-1 data gradient, weight gradient.
-// A tile is ngrp groups of 4 rows x nseg runs of SL columns, one (group, run) per wave.  SF_DW_ROT=0 keeps sf_dwsweep_kernel.
+// A tile is ngrp groups of 4 rows x nseg runs of SL columns, one (group, run) per wave.
 // strides >= 3 (windows do not overlap): forward and weight gradient on sf_dwrot_kernel<., 3, ...> (packed staging), data
 // gradient on sf_dwgap_dgrad_kernel
 static bool dwgap_shape_ok(const sf_dw_desc* d) {
@@ -1743,10 +1660,7 @@ static bool dwgap_shape_ok(const sf_dw_desc* d) {
     return d->C % 8 == 0 && d->Cw % 8 == 0;
 }
 static bool dwrot_plan(const sf_dw_desc* d, int dir, DwSweepParams& p, int& kmode, int& ks, int& ksl) {
-    const char* lv = getenv("SF_DW_ROT");
-    if (lv && atoi(lv) == 0) return false;
-    lv = getenv("SF_DW_SWEEP");
-    if (lv && atoi(lv) == 0) return false;
+    if (test_hook("SF_DW_SWEEP", 1) == 0) return false;
     const bool gap = dwgap_shape_ok(d);
     if (!dwsweep_shape_ok(d) && !gap) return false;
     if (dir == 1 && d->sH != 1) return false;           // stride 2: sf_dwsweep_kernel<1, 2>; strides >= 3: sf_dwgap_dgrad_kernel
@@ -1760,9 +1674,8 @@ static bool dwrot_plan(const sf_dw_desc* d, int dir, DwSweepParams& p, int& kmod
     else { kmode = 2; ks = s; p.Ha = d->Hi; p.Wa = d->Wi; p.Hb = d->Ho; p.Wb = d->Wo; p.Hit = d->Ho; p.Wit = d->Wo; }
     const int lds_cap = ks == 1 ? DwrLds<0, 1>::bytes : DwrLds<0, 2>::bytes;
     const int64_t max_rows = gap ? (int64_t)d->N * d->Ho * d->Wo : dwsweep_max_rows(d);
-    auto env_int = [](const char* n) { const char* e = getenv(n); return e ? atoi(e) : 0; };
-    const int f_sl = env_int("SF_DWR_SL"), f_grp = env_int("SF_DWR_NGRP"), f_seg = env_int("SF_DWR_NSEG");         // tests / tuning
-    const int f_nr = env_int("SF_DWR_NR");
+    const int f_sl = test_hook("SF_DWR_SL", 0), f_grp = test_hook("SF_DWR_NGRP", 0), f_seg = test_hook("SF_DWR_NSEG", 0);  // tests / tuning
+    const int f_nr = test_hook("SF_DWR_NR", 0);
     double best = 0.0;
     static const int kSL[2] = {7, 4};
     for (int si = 0; si < 2; ++si) {
@@ -1835,20 +1748,30 @@ static void dwrot_launch(DwSweepParams& p, int kmode, int ks, int sl, bool stats
 #undef SF_DWR_SL
 #undef SF_DWR_LAUNCH
 }
-static void dwsweep_launch(DwSweepParams& p, int kmode, int ks, bool stats, hipStream_t s) {
+static void dwsweep_launch(DwSweepParams& p, bool stats, hipStream_t s) {
     const dim3 grid((unsigned)(p.N * p.tiles_h * p.tiles_w * p.nchunks));
     static const bool trace = test_hook("SF_TRACE", 0) != 0;
-    if (trace) fprintf(stderr, "[sfamd] dwsweep: mode %d s=%d N=%d C=%d T=%d a %dx%d it %dx%d TH=%d TW=%d tiles %dx%d RA=%d CA=%d RP=%d slot %d "
-                       "(b %d) grp=%d seg=%d SL=%d blocks=%u\n", kmode, ks, p.N, p.C, p.T, p.Ha, p.Wa, p.Hit, p.Wit, p.TH, p.TW, p.tiles_h, p.tiles_w,
+    if (trace) fprintf(stderr, "[sfamd] dwsweep: mode 1 s=2 N=%d C=%d T=%d a %dx%d it %dx%d TH=%d TW=%d tiles %dx%d RA=%d CA=%d RP=%d slot %d "
+                       "(b %d) grp=%d seg=%d SL=%d blocks=%u\n", p.N, p.C, p.T, p.Ha, p.Wa, p.Hit, p.Wit, p.TH, p.TW, p.tiles_h, p.tiles_w,
                        p.RA, p.CA, p.RP, p.slotb, p.slotbB, p.ngrp, p.nseg, p.SL, grid.x);
-#define SF_DWS_LAUNCH(M, S, ST) hipLaunchKernelGGL((sf_dwsweep_kernel<M, S, ST>), grid, dim3(SF_THREADS), 0, s, p)
-    if (kmode == 0) {
-        if (ks == 1) { if (stats) SF_DWS_LAUNCH(0, 1, true); else SF_DWS_LAUNCH(0, 1, false); }
-        else { if (stats) SF_DWS_LAUNCH(0, 2, true); else SF_DWS_LAUNCH(0, 2, false); }
-    } else if (kmode == 1) { if (stats) SF_DWS_LAUNCH(1, 2, true); else SF_DWS_LAUNCH(1, 2, false); }
-    else if (ks == 1) SF_DWS_LAUNCH(2, 1, false);
-    else SF_DWS_LAUNCH(2, 2, false);
-#undef SF_DWS_LAUNCH
+    if (stats) hipLaunchKernelGGL((sf_dwsweep_kernel<1, 2, true>), grid, dim3(SF_THREADS), 0, s, p);
+    else hipLaunchKernelGGL((sf_dwsweep_kernel<1, 2, false>), grid, dim3(SF_THREADS), 0, s, p);
+}
+// Data gradient at strides >= 3 (sf_dwgap_dgrad_kernel): one thread per (input position, 8 channels)
+static bool dwgap_plan(const sf_dw_desc* d, DwGapParams& gp, int& blocks) {
+    if (test_hook("SF_DW_SWEEP", 1) == 0 || !dwgap_shape_ok(d) || 27 * d->Cw > SF_DW_GAP_W) return false;
+    memset(&gp, 0, sizeof(gp));
+    gp.N = d->N; gp.C = d->C; gp.Cw = d->Cw; gp.Cwreal = d->Cwreal ? d->Cwreal : d->Cw; gp.cls = d->cls ? 1 : 0;
+    gp.T = d->Ti; gp.Hi = d->Hi; gp.Wi = d->Wi; gp.Ho = d->Ho; gp.Wo = d->Wo; gp.s = d->sH;
+    const int64_t Si = (int64_t)d->Ti * d->Hi * d->Wi + gp.cls;
+    gp.rows = (int64_t)d->N * Si;
+    const int64_t items = gp.rows * (d->C / 8);
+    if (items >= (1ll << 31)) return false;             // the kernel splits (uint32_t)item with fd_divmod: exact below 2^31 (sf_common.h)
+    gp.fdRow = make_fastdiv((uint32_t)Si); gp.fdW = make_fastdiv(d->Wi); gp.fdH = make_fastdiv(d->Hi);
+    gp.fdS = make_fastdiv(d->sH); gp.fdG = make_fastdiv(d->C / 8);
+    blocks = cdiv(items, SF_THREADS * 4);
+    if (blocks > 4096) blocks = 4096;
+    return true;
 }
 
 // Temporal depthwise convolution (kT, 1, 1) / stride 1 / padding kT / 2 (X3D stem): one register-window pass (sf_dwtemporal.h).
@@ -1888,112 +1811,138 @@ static void dwtemp_launch(DwTempParams& p, int kT, int dir, bool stats, hipStrea
 #undef SF_DWTP_LAUNCH
 }
 
+// ------------------------------------------------------------------------------------------------
+// One plan per call: the family that runs a depthwise convolution, its filled parameters and the rows of its side table.  Every
+// launcher and every size query (sf_dwconv_fwd_blocks, _fwd_sample_rows, _dgrad_sum_rows, _pair_ok) reads this one function, so
+// the tables a caller allocates agree with what runs.  dir: 0 forward, 1 data gradient, 2 weight gradient.  side_table: the call
+// writes the forward's BatchNorm partial sums / the data gradient's column sums.
+// Precedence: temporal (kT, 1, 1) window; the plane sweeps (rotating form, the stride-2 data gradient, the gap data gradient at
+// strides >= 3); the W-blocked stencils; the generic stencils.
+enum DwFamily { DW_TEMPORAL, DW_ROT, DW_SWEEP, DW_GAP, DW_BLOCKED, DW_GENERIC };
+struct DwPlan {
+    DwFamily fam;
+    int64_t rows;           // side table rows: [rows][2][C] sums (dir 0 / 1; 0: this family leaves no column sums), [rows][taps][C] (dir 2)
+    DwParams p; dim3 grid; DwBlockIdx bi; int kind;     // stencils (kind: dw_blocked_kind, 0 = generic)
+    DwTempParams tp;
+    DwSweepParams sp; int km, ks, sl;                   // DW_ROT (kernel mode, template stride, run length) / DW_SWEEP
+    DwGapParams gp; int gblocks;
+};
+static int dw_plan(DwPlan& pl, const sf_dw_desc* d, int dir, bool side_table) {
+    static const int kMaxBlocks[3] = {kDwFwdBlocks, 8192, kDwWgradBlocks};      // stencil row blocks per direction
+    if (fill_dw(pl.p, d, dir != 1, kMaxBlocks[dir], pl.grid)) return -1;
+    pl.rows = 0;
+    pl.kind = 0;
+    if (dwtemp_plan(d, dir, pl.tp)) {
+        pl.fam = DW_TEMPORAL;
+        if (dir != 1) pl.rows = dwtemp_blocks(pl.tp);
+        return 0;
+    }
+    // with BatchNorm sums a cls row keeps the forward on the stencils (the sums on the sweeps serve X3D, which has no cls row)
+    if (!(dir == 0 && side_table && d->cls) && dwrot_plan(d, dir, pl.sp, pl.km, pl.ks, pl.sl)) pl.fam = DW_ROT;
+    else if (dir == 1 && dwsweep_plan(d, pl.sp)) pl.fam = DW_SWEEP;
+    else if (dir == 1 && dwgap_plan(d, pl.gp, pl.gblocks)) { pl.fam = DW_GAP; return 0; }
+    else {
+        pl.kind = dw_blocked_kind(d);
+        pl.fam = pl.kind ? DW_BLOCKED : DW_GENERIC;
+        if (pl.kind) dw_block_plan(pl.p, pl.bi, d, dir != 1, kMaxBlocks[dir], pl.grid);
+        if (dir != 1) pl.rows = pl.grid.x;
+        return 0;
+    }
+    pl.rows = (int64_t)pl.sp.N * pl.sp.tiles_h * pl.sp.tiles_w;     // one row per (sample, tile)
+    return 0;
+}
+static void dw_sweep_launch(DwPlan& pl, bool stats, hipStream_t s) {
+    if (pl.fam == DW_ROT) dwrot_launch(pl.sp, pl.km, pl.ks, pl.sl, stats, s);
+    else dwsweep_launch(pl.sp, stats, s);
+}
+// sums the [nblk][taps][ldc] partial rows of a weight gradient into dw (ldc = 0: C)
+static void dw_wgrad_finalize(const sf_dw_desc* d, const float* wpart, int nblk, int ldc, float* dw, float scale, int zero_first,
+                              hipStream_t s) {
+    DwFinalizeParams f;
+    f.wpart = wpart; f.nblk = nblk; f.taps = d->kT * d->kH * d->kW; f.C = d->C; f.Cw = d->Cw; f.ldc = ldc;
+    f.Cwreal = d->Cwreal ? d->Cwreal : d->Cw;
+    f.dw = dw; f.scale = scale; f.accumulate = zero_first ? 0 : 1;
+    hipLaunchKernelGGL(sf_dwconv_wgrad_finalize_kernel, dim3(cdiv(f.taps * d->Cw, 32)), dim3(SF_THREADS), 0, s, f);
+}
+
+// rows of sf_dwconv_fwd's statistics table
 extern "C" int sf_dwconv_fwd_blocks(const sf_dw_desc* d) {
-    DwParams p;
-    dim3 grid;
-    if (fill_dw(p, d, true, kDwFwdBlocks, grid)) return -1;
-    {
-        DwTempParams tp;
-        if (dwtemp_plan(d, 0, tp)) return dwtemp_blocks(tp);
-    }
-    if (!d->cls) {      // the sweep carries the BatchNorm partial sums: one row per (sample, tile)
-        DwSweepParams sp;
-        int km, ks, sl;
-        if (dwrot_plan(d, 0, sp, km, ks, sl)) return sp.N * sp.tiles_h * sp.tiles_w;
-        if (dwsweep_plan(d, 0, sp, km, ks)) return sp.N * sp.tiles_h * sp.tiles_w;
-    }
-    if (dw_blocked_kind(d)) {
-        DwBlockIdx bi;
-        dw_block_plan(p, bi, d, true, kDwFwdBlocks, grid);
-    }
-    return (int)grid.x;
+    DwPlan pl;
+    if (dw_plan(pl, d, 0, true)) return -1;
+    return (int)pl.rows;
 }
 // Rows of sf_dwconv_fwd's statistics table that belong to ONE sample when the table is sample-major (the plane sweeps write one
 // row per (sample, tile): rows [n * r, (n + 1) * r) are sample n's), 0 when the kernel this geometry takes cuts its rows without
 // regard to samples.  Lets a caller take per-sample channel sums (the SE squeeze, operators.py:38-45) from the table instead of
 // from a pass over y.
 extern "C" int sf_dwconv_fwd_sample_rows(const sf_dw_desc* d) {
-    DwParams p;
-    dim3 grid;
-    if (fill_dw(p, d, true, kDwFwdBlocks, grid)) return -1;
-    DwTempParams tp;
-    if (dwtemp_plan(d, 0, tp)) return 0;
-    if (!d->cls) {
-        DwSweepParams sp;
-        int km, ks, sl;
-        if (dwrot_plan(d, 0, sp, km, ks, sl)) return sp.tiles_h * sp.tiles_w;
-        if (dwsweep_plan(d, 0, sp, km, ks)) return sp.tiles_h * sp.tiles_w;
-    }
-    return 0;
+    DwPlan pl;
+    if (dw_plan(pl, d, 0, true)) return -1;
+    return pl.fam == DW_ROT ? pl.sp.tiles_h * pl.sp.tiles_w : 0;
 }
 extern "C" int sf_dwconv_fwd(const sf_dw_desc* d, const void* x, const float* w, void* y, float* stat_part,
                              sf_stream_t stream) {
-    DwParams p;
-    dim3 grid;
-    if (fill_dw(p, d, true, kDwFwdBlocks, grid)) return -1;
+    DwPlan pl;
+    if (dw_plan(pl, d, 0, stat_part != nullptr)) return -1;
     REQUIRE(x && w && y, "sf_dwconv_fwd: null pointer");
-    {
-        DwTempParams tp;
-        if (dwtemp_plan(d, 0, tp)) {
-            tp.a = (const f16*)x; tp.lda = d->ldx; tp.dst = (f16*)y; tp.ldd = d->ldy; tp.w = w; tp.part = stat_part;
-            dwtemp_launch(tp, d->kT, 0, stat_part != nullptr, (hipStream_t)stream);
-            return check_launch("dwconv_fwd (temporal)");
-        }
+    hipStream_t s = (hipStream_t)stream;
+    if (pl.fam == DW_TEMPORAL) {
+        DwTempParams& tp = pl.tp;
+        tp.a = (const f16*)x; tp.lda = d->ldx; tp.dst = (f16*)y; tp.ldd = d->ldy; tp.w = w; tp.part = stat_part;
+        dwtemp_launch(tp, d->kT, 0, stat_part != nullptr, s);
+        return check_launch("dwconv_fwd (temporal)");
     }
-    if (!(stat_part && d->cls)) {
-        DwSweepParams sp;
-        int km, ks, sl;
-        if (dwrot_plan(d, 0, sp, km, ks, sl)) {
-            sp.a = (const f16*)x; sp.lda = d->ldx; sp.dst = (f16*)y; sp.ldd = d->ldy; sp.w = w; sp.part = stat_part;
-            dwrot_launch(sp, km, ks, sl, stat_part != nullptr, (hipStream_t)stream);
-            return check_launch("dwconv_fwd (rot)");
-        }
-        if (dwsweep_plan(d, 0, sp, km, ks)) {
-            sp.a = (const f16*)x; sp.lda = d->ldx; sp.dst = (f16*)y; sp.ldd = d->ldy; sp.w = w; sp.part = stat_part;
-            dwsweep_launch(sp, km, ks, stat_part != nullptr, (hipStream_t)stream);
-            return check_launch("dwconv_fwd (sweep)");
-        }
+    if (pl.fam == DW_ROT) {
+        DwSweepParams& sp = pl.sp;
+        sp.a = (const f16*)x; sp.lda = d->ldx; sp.dst = (f16*)y; sp.ldd = d->ldy; sp.w = w; sp.part = stat_part;
+        dw_sweep_launch(pl, stat_part != nullptr, s);
+        return check_launch("dwconv_fwd (rot)");
     }
-    {
-        DwTileParams tp;
-        int np;
-        if (!stat_part && dwtile_plan(d, 0, tp, np)) {
-            tp.src = (const f16*)x; tp.ld_src = d->ldx; tp.dst = (f16*)y; tp.ld_dst = d->ldy; tp.w = w;
-            dwtile_launch(tp, np, (hipStream_t)stream);
-            return check_launch("dwconv_fwd (tiled)");
-        }
-    }
+    DwParams& p = pl.p;
     p.x = (const f16*)x; p.ldx = d->ldx; p.w = w; p.y = (f16*)y; p.ldy = d->ldy; p.stat_part = stat_part;
-    const int kind = dw_blocked_kind(d);
-    if (kind) {
-        DwBlockIdx bi;
-        dw_block_plan(p, bi, d, true, kDwFwdBlocks, grid);
-        SF_DW_DISPATCH_WT(kind, sf_dwconv_fwd_blocked_kernel, grid, (hipStream_t)stream, p, bi);
-    } else {
-        if (p.kT * p.kH * p.kW * p.Cw <= SF_DW_SMALL_W)
-            hipLaunchKernelGGL(sf_dwconv_fwd_kernel<SF_DW_SMALL_W>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL(sf_dwconv_fwd_kernel<SF_DW_MAX_W>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
-    }
+    if (pl.kind) SF_DW_DISPATCH_WT(pl.kind, sf_dwconv_fwd_blocked_kernel, pl.grid, s, p, pl.bi);
+    else if (p.kT * p.kH * p.kW * p.Cw <= SF_DW_SMALL_W) hipLaunchKernelGGL(sf_dwconv_fwd_kernel<SF_DW_SMALL_W>, pl.grid, dim3(SF_THREADS), 0, s, p);
+    else hipLaunchKernelGGL(sf_dwconv_fwd_kernel<SF_DW_MAX_W>, pl.grid, dim3(SF_THREADS), 0, s, p);
     return check_launch("dwconv_fwd");
 }
 // rows of the optional column-sum table of sf_dwconv_dgrad_sums ([rows][2][C]: slot 0 = per-workgroup column sums of dx, the
 // cls row included; slot 1 unspecified), 0 when the kernel this geometry takes cannot leave them
-static int dw_dgrad_sum_rows(const sf_dw_desc* d) {
-    DwTempParams tp;
-    if (dwtemp_plan(d, 1, tp)) return 0;
-    DwSweepParams sp;
-    int km, ks, sl;
-    if (dwrot_plan(d, 1, sp, km, ks, sl) || dwsweep_plan(d, 1, sp, km, ks)) return sp.N * sp.tiles_h * sp.tiles_w;
-    return 0;
-}
 extern "C" int sf_dwconv_dgrad_sum_rows(const sf_dw_desc* d) {
-    DwParams p;
-    dim3 grid;
-    if (fill_dw(p, d, false, 8192, grid)) return -1;
-    return dw_dgrad_sum_rows(d);
+    DwPlan pl;
+    if (dw_plan(pl, d, 1, true)) return -1;
+    return (int)pl.rows;
 }
-static int dwconv_dgrad_impl(const sf_dw_desc* d, const void* dy, const float* w, void* dx, float* sum_part, sf_stream_t stream);
+static int dwconv_dgrad_impl(const sf_dw_desc* d, const void* dy, const float* w, void* dx, float* sum_part, sf_stream_t stream) {
+    DwPlan pl;
+    if (dw_plan(pl, d, 1, sum_part != nullptr)) return -1;
+    REQUIRE(!sum_part || pl.rows > 0, "sf_dwconv_dgrad_sums: this geometry leaves no column sums (sf_dwconv_dgrad_sum_rows == 0)");
+    REQUIRE(dy && w && dx, "sf_dwconv_dgrad: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (pl.fam == DW_TEMPORAL) {
+        DwTempParams& tp = pl.tp;
+        tp.a = (const f16*)dy; tp.lda = d->ldy; tp.dst = (f16*)dx; tp.ldd = d->ldx; tp.w = w;
+        dwtemp_launch(tp, d->kT, 1, false, s);
+        return check_launch("dwconv_dgrad (temporal)");
+    }
+    if (pl.fam == DW_ROT || pl.fam == DW_SWEEP) {
+        DwSweepParams& sp = pl.sp;
+        sp.a = (const f16*)dy; sp.lda = d->ldy; sp.dst = (f16*)dx; sp.ldd = d->ldx; sp.w = w; sp.part = sum_part;
+        dw_sweep_launch(pl, sum_part != nullptr, s);
+        return check_launch(pl.fam == DW_ROT ? "dwconv_dgrad (rot)" : "dwconv_dgrad (sweep)");
+    }
+    if (pl.fam == DW_GAP) {
+        DwGapParams& gp = pl.gp;
+        gp.dy = (const f16*)dy; gp.lddy = d->ldy; gp.dx = (f16*)dx; gp.lddx = d->ldx; gp.w = w;
+        hipLaunchKernelGGL(sf_dwgap_dgrad_kernel, dim3(pl.gblocks), dim3(SF_THREADS), 0, s, gp);
+        return check_launch("dwconv_dgrad (gap)");
+    }
+    DwParams& p = pl.p;
+    p.dy = (const f16*)dy; p.lddy = d->ldy; p.w = w; p.y = (f16*)dx; p.ldy = d->ldx;
+    if (pl.kind) SF_DW_DISPATCH_WT(pl.kind, sf_dwconv_dgrad_blocked_kernel, pl.grid, s, p, pl.bi);
+    else if (p.kT * p.kH * p.kW * p.Cw <= SF_DW_SMALL_W) hipLaunchKernelGGL(sf_dwconv_dgrad_kernel<SF_DW_SMALL_W>, pl.grid, dim3(SF_THREADS), 0, s, p);
+    else hipLaunchKernelGGL(sf_dwconv_dgrad_kernel<SF_DW_MAX_W>, pl.grid, dim3(SF_THREADS), 0, s, p);
+    return check_launch("dwconv_dgrad");
+}
 extern "C" int sf_dwconv_dgrad(const sf_dw_desc* d, const void* dy, const float* w, void* dx, sf_stream_t stream) {
     return dwconv_dgrad_impl(d, dy, w, dx, nullptr, stream);
 }
@@ -2002,80 +1951,7 @@ extern "C" int sf_dwconv_dgrad(const sf_dw_desc* d, const void* dy, const float*
 extern "C" int sf_dwconv_dgrad_sums(const sf_dw_desc* d, const void* dy, const float* w, void* dx, float* sum_part,
                                     sf_stream_t stream) {
     REQUIRE(sum_part, "sf_dwconv_dgrad_sums: null table");
-    DwParams p;
-    dim3 grid;
-    if (fill_dw(p, d, false, 8192, grid)) return -1;
-    REQUIRE(dw_dgrad_sum_rows(d) > 0, "sf_dwconv_dgrad_sums: this geometry leaves no column sums (sf_dwconv_dgrad_sum_rows == 0)");
     return dwconv_dgrad_impl(d, dy, w, dx, sum_part, stream);
-}
-static int dwconv_dgrad_impl(const sf_dw_desc* d, const void* dy, const float* w, void* dx, float* sum_part, sf_stream_t stream) {
-    DwParams p;
-    dim3 grid;
-    if (fill_dw(p, d, false, 8192, grid)) return -1;
-    REQUIRE(dy && w && dx, "sf_dwconv_dgrad: null pointer");
-    {
-        DwTempParams tp;
-        if (dwtemp_plan(d, 1, tp)) {
-            tp.a = (const f16*)dy; tp.lda = d->ldy; tp.dst = (f16*)dx; tp.ldd = d->ldx; tp.w = w;
-            dwtemp_launch(tp, d->kT, 1, false, (hipStream_t)stream);
-            return check_launch("dwconv_dgrad (temporal)");
-        }
-    }
-    {
-        DwSweepParams sp;
-        int km, ks, sl;
-        if (dwrot_plan(d, 1, sp, km, ks, sl)) {
-            sp.a = (const f16*)dy; sp.lda = d->ldy; sp.dst = (f16*)dx; sp.ldd = d->ldx; sp.w = w; sp.part = sum_part;
-            dwrot_launch(sp, km, ks, sl, sum_part != nullptr, (hipStream_t)stream);
-            return check_launch("dwconv_dgrad (rot)");
-        }
-        if (dwsweep_plan(d, 1, sp, km, ks)) {
-            sp.a = (const f16*)dy; sp.lda = d->ldy; sp.dst = (f16*)dx; sp.ldd = d->ldx; sp.w = w; sp.part = sum_part;
-            dwsweep_launch(sp, km, ks, sum_part != nullptr, (hipStream_t)stream);
-            return check_launch("dwconv_dgrad (sweep)");
-        }
-        const char* lv = getenv("SF_DW_SWEEP");
-        if (dwgap_shape_ok(d) && !(lv && atoi(lv) == 0) && 27 * d->Cw <= SF_DW_GAP_W) {
-            DwGapParams gp;
-            memset(&gp, 0, sizeof(gp));
-            gp.dy = (const f16*)dy; gp.lddy = d->ldy; gp.dx = (f16*)dx; gp.lddx = d->ldx; gp.w = w;
-            gp.N = d->N; gp.C = d->C; gp.Cw = d->Cw; gp.Cwreal = d->Cwreal ? d->Cwreal : d->Cw; gp.cls = d->cls ? 1 : 0;
-            gp.T = d->Ti; gp.Hi = d->Hi; gp.Wi = d->Wi; gp.Ho = d->Ho; gp.Wo = d->Wo; gp.s = d->sH;
-            const int64_t Si = (int64_t)d->Ti * d->Hi * d->Wi + gp.cls;
-            gp.rows = (int64_t)d->N * Si;
-            if (gp.rows * (d->C / 8) < (1ll << 32)) {
-                gp.fdRow = make_fastdiv((uint32_t)Si); gp.fdW = make_fastdiv(d->Wi); gp.fdH = make_fastdiv(d->Hi);
-                gp.fdS = make_fastdiv(d->sH); gp.fdG = make_fastdiv(d->C / 8);
-                const int64_t items = gp.rows * (d->C / 8);
-                int blocks = cdiv(items, SF_THREADS * 4);
-                if (blocks > 4096) blocks = 4096;
-                hipLaunchKernelGGL(sf_dwgap_dgrad_kernel, dim3(blocks), dim3(SF_THREADS), 0, (hipStream_t)stream, gp);
-                return check_launch("dwconv_dgrad (gap)");
-            }
-        }
-    }
-    {
-        DwTileParams tp;
-        int np;
-        if (dwtile_plan(d, 1, tp, np)) {
-            tp.src = (const f16*)dy; tp.ld_src = d->ldy; tp.dst = (f16*)dx; tp.ld_dst = d->ldx; tp.w = w;
-            dwtile_launch(tp, np, (hipStream_t)stream);
-            return check_launch("dwconv_dgrad (tiled)");
-        }
-    }
-    p.dy = (const f16*)dy; p.lddy = d->ldy; p.w = w; p.y = (f16*)dx; p.ldy = d->ldx;
-    const int kind = dw_blocked_kind(d);
-    if (kind) {
-        DwBlockIdx bi;
-        dw_block_plan(p, bi, d, false, 8192, grid);
-        SF_DW_DISPATCH_WT(kind, sf_dwconv_dgrad_blocked_kernel, grid, (hipStream_t)stream, p, bi);
-    } else {
-        if (p.kT * p.kH * p.kW * p.Cw <= SF_DW_SMALL_W)
-            hipLaunchKernelGGL(sf_dwconv_dgrad_kernel<SF_DW_SMALL_W>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
-        else
-            hipLaunchKernelGGL(sf_dwconv_dgrad_kernel<SF_DW_MAX_W>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
-    }
-    return check_launch("dwconv_dgrad");
 }
 // ------------------------------------------------------------------------------------------------
 // PAIR entry points (round 6): two depthwise convolutions of ONE geometry on two tensors in ONE launch per direction -- MViT's
@@ -2084,58 +1960,40 @@ static int dwconv_dgrad_impl(const sf_dw_desc* d, const void* dy, const float* w
 // tensors behind one start-up cost 1.45x one (tools/dw_bench.py: C = 768 against C = 384 at the same plane).  The descriptor
 // describes ONE tensor; the plane sweeps (sf_dwsweep.h, PAIR mode) must take the geometry in all three directions and C must be a
 // multiple of 32: sf_dwconv_pair_ok.  Same arithmetic as two single calls, bit for bit.
-static bool dw_sweep_plan_any(const sf_dw_desc* d, int dir, DwSweepParams& sp, int& km, int& ks, int& sl, bool& rot) {
-    sl = 0;
-    rot = dwrot_plan(d, dir, sp, km, ks, sl);
-    return rot || dwsweep_plan(d, dir, sp, km, ks);
-}
-static void dw_pair_setup(DwSweepParams& sp, const sf_dw_desc* d) {
-    sp.csplit = d->C; sp.Cpart = 2 * d->C; sp.nchunks *= 2;
-}
 extern "C" int sf_dwconv_pair_ok(const sf_dw_desc* d) {
-    DwParams p;
-    dim3 grid;
-    if (fill_dw(p, d, true, kDwFwdBlocks, grid)) return -1;
-    const char* lv = getenv("SF_DW_PAIR");
-    if (lv && atoi(lv) == 0) return 0;
-    if (d->C % 32 != 0) return 0;
-    DwTempParams tp;
-    if (dwtemp_plan(d, 0, tp)) return 0;
-    DwSweepParams sp;
-    int km, ks, sl;
-    bool rot;
+    DwPlan pl;
+    if (dw_plan(pl, d, 0, false)) return -1;
+    if (test_hook("SF_DW_PAIR", 1) == 0 || d->C % 32 != 0) return 0;
     for (int dir = 0; dir < 3; ++dir)
-        if (!dw_sweep_plan_any(d, dir, sp, km, ks, sl, rot)) return 0;
+        if ((dir > 0 && dw_plan(pl, d, dir, false)) || (pl.fam != DW_ROT && pl.fam != DW_SWEEP)) return 0;
     return 1;
+}
+static void dw_pair_plan(DwPlan& pl, const sf_dw_desc* d, int dir) {
+    dw_plan(pl, d, dir, false);         // (taken: sf_dwconv_pair_ok)
+    pl.sp.csplit = d->C; pl.sp.Cpart = 2 * d->C; pl.sp.nchunks *= 2;
 }
 extern "C" int sf_dwconv_fwd_pair(const sf_dw_desc* d, const void* x, const void* x2, const float* w, const float* w2, void* y,
                                   void* y2, sf_stream_t stream) {
     REQUIRE(sf_dwconv_pair_ok(d) == 1, "sf_dwconv_fwd_pair: geometry not taken (sf_dwconv_pair_ok)");
     REQUIRE(x && x2 && w && w2 && y && y2, "sf_dwconv_fwd_pair: null pointer");
-    DwSweepParams sp;
-    int km, ks, sl;
-    bool rot;
-    dw_sweep_plan_any(d, 0, sp, km, ks, sl, rot);
-    dw_pair_setup(sp, d);
+    DwPlan pl;
+    dw_pair_plan(pl, d, 0);
+    DwSweepParams& sp = pl.sp;
     sp.a = (const f16*)x; sp.a2 = (const f16*)x2; sp.lda = d->ldx; sp.dst = (f16*)y; sp.dst2 = (f16*)y2; sp.ldd = d->ldy;
     sp.w = w; sp.w2 = w2;
-    if (rot) dwrot_launch(sp, km, ks, sl, false, (hipStream_t)stream);
-    else dwsweep_launch(sp, km, ks, false, (hipStream_t)stream);
+    dw_sweep_launch(pl, false, (hipStream_t)stream);
     return check_launch("dwconv_fwd_pair");
 }
 extern "C" int sf_dwconv_dgrad_pair(const sf_dw_desc* d, const void* dy, const void* dy2, const float* w, const float* w2,
                                     void* dx, void* dx2, sf_stream_t stream) {
     REQUIRE(sf_dwconv_pair_ok(d) == 1, "sf_dwconv_dgrad_pair: geometry not taken (sf_dwconv_pair_ok)");
     REQUIRE(dy && dy2 && w && w2 && dx && dx2, "sf_dwconv_dgrad_pair: null pointer");
-    DwSweepParams sp;
-    int km, ks, sl;
-    bool rot;
-    dw_sweep_plan_any(d, 1, sp, km, ks, sl, rot);
-    dw_pair_setup(sp, d);
+    DwPlan pl;
+    dw_pair_plan(pl, d, 1);
+    DwSweepParams& sp = pl.sp;
     sp.a = (const f16*)dy; sp.a2 = (const f16*)dy2; sp.lda = d->ldy; sp.dst = (f16*)dx; sp.dst2 = (f16*)dx2; sp.ldd = d->ldx;
     sp.w = w; sp.w2 = w2;
-    if (rot) dwrot_launch(sp, km, ks, sl, false, (hipStream_t)stream);
-    else dwsweep_launch(sp, km, ks, false, (hipStream_t)stream);
+    dw_sweep_launch(pl, false, (hipStream_t)stream);
     return check_launch("dwconv_dgrad_pair");
 }
 // workspace: 2 x sf_dwconv_wgrad_workspace(d) bytes
@@ -2144,92 +2002,22 @@ extern "C" int sf_dwconv_wgrad_pair(const sf_dw_desc* d, const void* x, const vo
                                     int64_t workspace_bytes, sf_stream_t stream) {
     REQUIRE(sf_dwconv_pair_ok(d) == 1, "sf_dwconv_wgrad_pair: geometry not taken (sf_dwconv_pair_ok)");
     REQUIRE(x && x2 && dy && dy2 && dw && dw2 && workspace, "sf_dwconv_wgrad_pair: null pointer");
-    DwSweepParams sp;
-    int km, ks, sl;
-    bool rot;
-    dw_sweep_plan_any(d, 2, sp, km, ks, sl, rot);
-    dw_pair_setup(sp, d);
-    const int taps = 27, nblk = sp.N * sp.tiles_h * sp.tiles_w;
-    REQUIRE(workspace_bytes >= (int64_t)nblk * taps * 2 * d->C * 4, "sf_dwconv_wgrad_pair: workspace too small");
+    DwPlan pl;
+    dw_pair_plan(pl, d, 2);
+    REQUIRE(workspace_bytes >= pl.rows * 27 * 2 * d->C * 4, "sf_dwconv_wgrad_pair: workspace too small");
+    DwSweepParams& sp = pl.sp;
     sp.a = (const f16*)x; sp.a2 = (const f16*)x2; sp.lda = d->ldx; sp.b = (const f16*)dy; sp.b2 = (const f16*)dy2; sp.ldb = d->ldy;
     sp.part = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
-    if (rot) dwrot_launch(sp, km, ks, sl, false, s);
-    else dwsweep_launch(sp, km, ks, false, s);
+    dw_sweep_launch(pl, false, s);
     if (check_launch("dwconv_wgrad_pair")) return -1;
-    for (int h = 0; h < 2; ++h) {
-        DwFinalizeParams f;
-        f.wpart = (const float*)workspace + (h ? d->C : 0); f.nblk = nblk; f.taps = taps; f.C = d->C; f.Cw = d->Cw; f.ldc = 2 * d->C;
-        f.Cwreal = d->Cwreal ? d->Cwreal : d->Cw;
-        f.dw = h ? dw2 : dw; f.scale = out_scale; f.accumulate = (h ? zero_first2 : zero_first) ? 0 : 1;
-        hipLaunchKernelGGL(sf_dwconv_wgrad_finalize_kernel, dim3(cdiv(taps * d->Cw, 32)), dim3(SF_THREADS), 0, s, f);
-    }
+    dw_wgrad_finalize(d, (const float*)workspace, (int)pl.rows, 2 * d->C, dw, out_scale, zero_first, s);
+    dw_wgrad_finalize(d, (const float*)workspace + d->C, (int)pl.rows, 2 * d->C, dw2, out_scale, zero_first2, s);
     return check_launch("dwconv_wgrad_pair_finalize");
 }
 
-// LDS-tiled weight gradient (sf_dwtile.h: sf_dwtile_wgrad_kernel).  SF_DW_WGRAD_TILED=0 keeps the stencils (A/B runs).
-static bool dwtile_wgrad_shape_ok(const sf_dw_desc* d) {
-    if (d->kT != 3 || d->kH != 3 || d->kW != 3 || d->pT != 1 || d->pH != 1 || d->pW != 1) return false;
-    if (d->sT != 1 || d->sH != d->sW || (d->sH != 1 && d->sH != 2) || d->To != d->Ti) return false;
-    return d->C % SF_DWT_CC == 0 && d->Wi <= 16;        // wider planes: the stencil is as fast (sf_dwtile.h)
-}
-static bool dwtile_wgrad_plan(const sf_dw_desc* d, DwTileWgradParams& p, int& cls_lds) {
-    const char* lv = getenv("SF_DW_WGRAD_TILED");   // read per call (tests switch it mid-process)
-    if (lv && atoi(lv) == 0) return false;
-    if (!dwtile_wgrad_shape_ok(d)) return false;
-    memset(&p, 0, sizeof(p));
-    p.N = d->N; p.C = d->C; p.cls = d->cls ? 1 : 0; p.T = d->Ti;
-    p.Hi = d->Hi; p.Wi = d->Wi; p.Ho = d->Ho; p.Wo = d->Wo; p.s = d->sH;
-    p.CT = p.Wi + 2;
-    p.rowf = p.CT * SF_DWW_PP + 16;
-    p.nchunks = d->C / SF_DWT_CC;
-    double best = 0.0;
-    int best_th = 0;
-    int best_cls = 0;
-    const char* e = getenv("SF_DWT_TH");            // tests force a row-tile height (read per call)
-    const int force_th = e ? atoi(e) : 0;
-    for (int th = p.Ho < 64 ? p.Ho : 64; th >= 1; --th) {
-        if (force_th > 0 && th != (force_th < p.Ho ? force_th : p.Ho)) continue;
-        const int rt = (th - 1) * p.s + 3;
-        const int64_t xf = (int64_t)rt * p.rowf, dp = (int64_t)th * p.Wo * SF_DWT_CC + 32;
-        if ((int64_t)rt * p.CT * SF_DWT_G > SF_THREADS * SF_DWT_VPT || (int64_t)th * p.Wo * SF_DWT_G > SF_THREADS * SF_DWW_VPT) continue;
-        // LDS class: 0 = 47 KiB (three workgroups per CU), 1 = large x tile + small dy slots, 67 KiB (two), 2 = 85 KiB (one)
-        if (xf > SF_DWW_XF_L || dp > SF_DWW_DP_L) continue;
-        const int lc = xf <= SF_DWW_XF_S && dp <= SF_DWW_DP_S ? 0 : dp <= SF_DWW_DP_S ? 1 : 2;
-        const bool small = lc == 0;
-        const double resid = lc == 0 ? 1.0 : lc == 1 ? 0.75 : 0.5;
-        const int tiles = cdiv(p.Ho, th);
-        // rows are cut into nseg pieces of >= 4 positions: the cut that loads the seven subsets most evenly (fewest pieces on a tie)
-        int nseg = 0;
-        double balance = 0.0;
-        for (int ns = cdiv(p.Wo, 16); ns <= (p.Wo >= 4 ? p.Wo / 4 : 1); ++ns) {
-            const int items = th * ns, nsub = items < SF_DWW_SUBMAX ? items : SF_DWW_SUBMAX;
-            const double b = (double)items / ((double)cdiv(items, nsub) * SF_DWW_SUBMAX);     // busy share of the 7 subsets
-            if (b > balance + 1e-9) { balance = b; nseg = ns; }
-        }
-        if (!nseg) { nseg = 1; balance = (double)(th < SF_DWW_SUBMAX ? th : SF_DWW_SUBMAX) / SF_DWW_SUBMAX; }
-        const double rows = (double)p.Ho / ((double)tiles * th);                                 // useful rows of the tiles
-        const double halo = (double)(th * p.s) / rt;
-        const double blocks = (double)d->N * tiles * p.nchunks;
-        const double want = small ? 768.0 : lc == 1 ? 512.0 : 256.0;
-        const double fill = blocks >= want ? 1.0 : blocks / want;
-        const double quality = balance * rows * halo * resid;
-        if (quality < 0.3 && force_th <= 0) continue;       // badly filled tiles: the stencil is the better kernel
-        const double score = quality * fill;
-        if (score > best) { best = score; best_th = th; best_cls = lc; p.nseg = nseg; }
-    }
-    if (!best_th) return false;
-    p.TH = best_th; p.RT = (best_th - 1) * p.s + 3;
-    p.tiles_h = cdiv(p.Ho, best_th);
-    p.SL = cdiv(p.Wo, p.nseg);
-    p.nitems = best_th * p.nseg;
-    p.nsub = p.nitems < SF_DWW_SUBMAX ? p.nitems : SF_DWW_SUBMAX;
-    p.fdCT = make_fastdiv(p.CT); p.fdG = make_fastdiv(SF_DWT_G); p.fdWo = make_fastdiv(p.Wo); p.fdSeg = make_fastdiv(p.nseg);
-    cls_lds = best_cls;
-    const int64_t per_n_x = (int64_t)p.T * p.Hi * p.Wi + p.cls, per_n_dy = (int64_t)p.T * p.Ho * p.Wo + p.cls;
-    if (per_n_x * d->ldx >= (1ll << 31) || per_n_dy * d->ldy >= (1ll << 31)) return false;
-    return true;
-}
+// Partial-table bytes of sf_dwconv_wgrad: a bound over every family a call may take, whatever the per-call test hooks
+// (SF_DW_SWEEP, SF_DW_TEMPORAL, SF_DWS_* / SF_DWR_* tilings) select -- callers cache the size per geometry.
 extern "C" int64_t sf_dwconv_wgrad_workspace(const sf_dw_desc* d) {
     DwParams p;
     dim3 grid;
@@ -2238,109 +2026,41 @@ extern "C" int64_t sf_dwconv_wgrad_workspace(const sf_dw_desc* d) {
         DwBlockIdx bi;
         dw_block_plan(p, bi, d, true, kDwWgradBlocks, grid);
     }
-    // the tiled kernel writes one row per (sample, row tile): at most N * Ho of them whatever tile height a later call plans
-    // (the size is cached by the callers; SF_DW_WGRAD_TILED / SF_DWT_TH are read per call)
-    int64_t rows = grid.x;
-    if (dwtile_wgrad_shape_ok(d) && (int64_t)d->N * d->Ho > rows) rows = (int64_t)d->N * d->Ho;
-    if (dwsweep_shape_ok(d) && dwsweep_max_rows(d) > rows) rows = dwsweep_max_rows(d);
-    if (dwgap_shape_ok(d) && (int64_t)d->N * d->Ho * d->Wo > rows) rows = (int64_t)d->N * d->Ho * d->Wo;
+    int64_t rows = grid.x;                                                              // stencils
+    if (dwsweep_shape_ok(d) && dwsweep_max_rows(d) > rows) rows = dwsweep_max_rows(d);  // rotating sweep, strides 1 / 2
+    if (dwgap_shape_ok(d) && (int64_t)d->N * d->Ho * d->Wo > rows) rows = (int64_t)d->N * d->Ho * d->Wo;   // strides >= 3
     if (rows < 1024) rows = 1024;       // sf_dwtemporal_kernel: at most 1024 partial rows
     return rows * d->kT * d->kH * d->kW * d->C * 4;
 }
 extern "C" int sf_dwconv_wgrad(const sf_dw_desc* d, const void* x, const void* dy, float* dw, float out_scale,
                                int zero_first, void* workspace, int64_t workspace_bytes, sf_stream_t stream) {
-    DwParams p;
-    dim3 grid;
-    if (fill_dw(p, d, true, kDwWgradBlocks, grid)) return -1;
+    DwPlan pl;
+    if (dw_plan(pl, d, 2, true)) return -1;
     REQUIRE(x && dy && dw && workspace, "sf_dwconv_wgrad: null pointer");
     const int taps = d->kT * d->kH * d->kW;
-    {
-        DwTempParams tp;
-        if (dwtemp_plan(d, 2, tp)) {
-            const int nblk = dwtemp_blocks(tp);
-            REQUIRE(workspace_bytes >= (int64_t)nblk * taps * d->C * 4, "sf_dwconv_wgrad: workspace too small");
-            tp.a = (const f16*)x; tp.lda = d->ldx; tp.b = (const f16*)dy; tp.ldb = d->ldy; tp.part = (float*)workspace;
-            hipStream_t s = (hipStream_t)stream;
-            dwtemp_launch(tp, d->kT, 2, false, s);
-            if (check_launch("dwconv_wgrad (temporal)")) return -1;
-            DwFinalizeParams f;
-            f.wpart = (const float*)workspace; f.nblk = nblk; f.taps = taps; f.C = d->C; f.Cw = d->Cw; f.ldc = 0;
-            f.Cwreal = d->Cwreal ? d->Cwreal : d->Cw;
-            f.dw = dw; f.scale = out_scale; f.accumulate = zero_first ? 0 : 1;
-            hipLaunchKernelGGL(sf_dwconv_wgrad_finalize_kernel, dim3(cdiv(taps * d->Cw, 32)), dim3(SF_THREADS), 0, s, f);
-            return check_launch("dwconv_wgrad_finalize");
-        }
+    REQUIRE(workspace_bytes >= pl.rows * taps * d->C * 4, "sf_dwconv_wgrad: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    if (pl.fam == DW_TEMPORAL) {
+        DwTempParams& tp = pl.tp;
+        tp.a = (const f16*)x; tp.lda = d->ldx; tp.b = (const f16*)dy; tp.ldb = d->ldy; tp.part = (float*)workspace;
+        dwtemp_launch(tp, d->kT, 2, false, s);
+    } else if (pl.fam == DW_ROT) {
+        DwSweepParams& sp = pl.sp;
+        sp.a = (const f16*)x; sp.lda = d->ldx; sp.b = (const f16*)dy; sp.ldb = d->ldy; sp.part = (float*)workspace;
+        dw_sweep_launch(pl, false, s);
+    } else {
+        REQUIRE(pl.grid.y == 1, "sf_dwconv_wgrad: C > 2048 is not supported");
+        DwParams& p = pl.p;
+        dim3 grid = pl.grid;
+        p.x = (const f16*)x; p.ldx = d->ldx; p.dy = (const f16*)dy; p.lddy = d->ldy; p.wpart = (float*)workspace;
+        grid.z = pl.kind ? d->kT : d->kT * cdiv(d->kH * d->kW, 9);
+        if (pl.kind == 1) hipLaunchKernelGGL((sf_dwconv_wgrad_blocked_kernel<3, 1, SF_DW_SMALL_W>), grid, dim3(SF_THREADS), 0, s, p, pl.bi);
+        else if (pl.kind == 2) hipLaunchKernelGGL((sf_dwconv_wgrad_blocked_kernel<3, 2, SF_DW_SMALL_W>), grid, dim3(SF_THREADS), 0, s, p, pl.bi);
+        else if (pl.kind) hipLaunchKernelGGL((sf_dwconv_wgrad_blocked_kernel<1, 1, SF_DW_SMALL_W>), grid, dim3(SF_THREADS), 0, s, p, pl.bi);
+        else hipLaunchKernelGGL(sf_dwconv_wgrad_kernel, grid, dim3(SF_THREADS), 0, s, p);
     }
-    {
-        DwSweepParams sp;
-        int km, ks, sl = 0;
-        const bool rot = dwrot_plan(d, 2, sp, km, ks, sl);
-        if (rot || dwsweep_plan(d, 2, sp, km, ks)) {
-            const int nblk = sp.N * sp.tiles_h * sp.tiles_w;
-            REQUIRE(workspace_bytes >= (int64_t)nblk * taps * d->C * 4, "sf_dwconv_wgrad: workspace too small");
-            sp.a = (const f16*)x; sp.lda = d->ldx; sp.b = (const f16*)dy; sp.ldb = d->ldy; sp.part = (float*)workspace;
-            hipStream_t s = (hipStream_t)stream;
-            if (rot) dwrot_launch(sp, km, ks, sl, false, s);
-            else dwsweep_launch(sp, km, ks, false, s);
-            if (check_launch("dwconv_wgrad (sweep)")) return -1;
-            DwFinalizeParams f;
-            f.wpart = (const float*)workspace; f.nblk = nblk; f.taps = taps; f.C = d->C; f.Cw = d->Cw; f.ldc = 0;
-            f.Cwreal = d->Cwreal ? d->Cwreal : d->Cw;
-            f.dw = dw; f.scale = out_scale; f.accumulate = zero_first ? 0 : 1;
-            hipLaunchKernelGGL(sf_dwconv_wgrad_finalize_kernel, dim3(cdiv(taps * d->Cw, 32)), dim3(SF_THREADS), 0, s, f);
-            return check_launch("dwconv_wgrad_finalize");
-        }
-    }
-    {
-        DwTileWgradParams tp;
-        int lc;
-        if (dwtile_wgrad_plan(d, tp, lc)) {
-            const int nblk = tp.N * tp.tiles_h;
-            REQUIRE(workspace_bytes >= (int64_t)nblk * taps * d->C * 4, "sf_dwconv_wgrad: workspace too small");
-            tp.x = (const f16*)x; tp.ldx = d->ldx; tp.dy = (const f16*)dy; tp.lddy = d->ldy; tp.wpart = (float*)workspace;
-            const dim3 tgrid((unsigned)(nblk * tp.nchunks));
-            hipStream_t s = (hipStream_t)stream;
-            static const bool trace = test_hook("SF_TRACE", 0) != 0;
-            if (trace) fprintf(stderr, "[sfamd] dwtile wgrad: N=%d C=%d T=%d %dx%d -> %dx%d s=%d TH=%d tiles=%d nsub=%d items=%d lds class %d blocks=%u\n", tp.N,
-                               tp.C, tp.T, tp.Hi, tp.Wi, tp.Ho, tp.Wo, tp.s, tp.TH, tp.tiles_h, tp.nsub, tp.nitems, lc, tgrid.x);
-#define SF_DWW_LAUNCH(S, XF, DP) hipLaunchKernelGGL((sf_dwtile_wgrad_kernel<S, XF, DP>), tgrid, dim3(SF_THREADS), 0, s, tp)
-            if (tp.s == 1) {
-                if (lc == 0) SF_DWW_LAUNCH(1, SF_DWW_XF_S, SF_DWW_DP_S);
-                else if (lc == 1) SF_DWW_LAUNCH(1, SF_DWW_XF_L, SF_DWW_DP_S);
-                else SF_DWW_LAUNCH(1, SF_DWW_XF_L, SF_DWW_DP_L);
-            } else {
-                if (lc == 0) SF_DWW_LAUNCH(2, SF_DWW_XF_S, SF_DWW_DP_S);
-                else if (lc == 1) SF_DWW_LAUNCH(2, SF_DWW_XF_L, SF_DWW_DP_S);
-                else SF_DWW_LAUNCH(2, SF_DWW_XF_L, SF_DWW_DP_L);
-            }
-#undef SF_DWW_LAUNCH
-            if (check_launch("dwconv_wgrad (tiled)")) return -1;
-            DwFinalizeParams f;
-            f.wpart = (const float*)workspace; f.nblk = nblk; f.taps = taps; f.C = d->C; f.Cw = d->Cw; f.ldc = 0;
-            f.Cwreal = d->Cwreal ? d->Cwreal : d->Cw;
-            f.dw = dw; f.scale = out_scale; f.accumulate = zero_first ? 0 : 1;
-            hipLaunchKernelGGL(sf_dwconv_wgrad_finalize_kernel, dim3(cdiv(taps * d->Cw, 32)), dim3(SF_THREADS), 0, s, f);
-            return check_launch("dwconv_wgrad_finalize");
-        }
-    }
-    const int kind = dw_blocked_kind(d);
-    DwBlockIdx bi;
-    if (kind) dw_block_plan(p, bi, d, true, kDwWgradBlocks, grid);
-    REQUIRE(workspace_bytes >= (int64_t)grid.x * taps * d->C * 4, "sf_dwconv_wgrad: workspace too small");
-    REQUIRE(grid.y == 1, "sf_dwconv_wgrad: C > 2048 is not supported");
-    p.x = (const f16*)x; p.ldx = d->ldx; p.dy = (const f16*)dy; p.lddy = d->ldy; p.wpart = (float*)workspace;
-    grid.z = kind ? d->kT : d->kT * cdiv(d->kH * d->kW, 9);
-    if (kind == 1) hipLaunchKernelGGL((sf_dwconv_wgrad_blocked_kernel<3, 1, SF_DW_SMALL_W>), grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p, bi);
-    else if (kind == 2) hipLaunchKernelGGL((sf_dwconv_wgrad_blocked_kernel<3, 2, SF_DW_SMALL_W>), grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p, bi);
-    else if (kind) hipLaunchKernelGGL((sf_dwconv_wgrad_blocked_kernel<1, 1, SF_DW_SMALL_W>), grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p, bi);
-    else hipLaunchKernelGGL(sf_dwconv_wgrad_kernel, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
-    if (check_launch("dwconv_wgrad")) return -1;
-    DwFinalizeParams f;
-    f.wpart = (const float*)workspace; f.nblk = grid.x; f.taps = taps; f.C = d->C; f.Cw = d->Cw; f.ldc = 0;
-    f.Cwreal = d->Cwreal ? d->Cwreal : d->Cw;
-    f.dw = dw; f.scale = out_scale; f.accumulate = zero_first ? 0 : 1;
-    hipLaunchKernelGGL(sf_dwconv_wgrad_finalize_kernel, dim3(cdiv(taps * d->Cw, 32)), dim3(SF_THREADS), 0,
-                       (hipStream_t)stream, f);
+    if (check_launch(pl.fam == DW_TEMPORAL ? "dwconv_wgrad (temporal)" : pl.fam == DW_ROT ? "dwconv_wgrad (rot)" : "dwconv_wgrad")) return -1;
+    dw_wgrad_finalize(d, (const float*)workspace, (int)pl.rows, 0, dw, out_scale, zero_first, s);
     return check_launch("dwconv_wgrad_finalize");
 }
 

@@ -1,37 +1,29 @@
-// Depthwise 3x3x3 convolution (padding 1, stride (1, s, s), s = 1 | 2) on channels-last rows: ring-buffered plane sweep with the
-// CHANNELS on the lanes (round 6).
+// Depthwise 3x3x3 convolution (padding 1, stride (1, s, s)) on channels-last rows: ring-buffered plane sweeps with the CHANNELS on
+// the lanes (round 6).
 //
 // Reference call sites: MViT pooling convolutions pool_q / pool_k / pool_v (slowfast/models/attention.py:13-45, 227-266) and the
 // X3D bottleneck's channelwise 3x3x3 (slowfast/models/resnet_helper.py:214-224), forward, data gradient and weight gradient.
 //
-// Why a third kernel family.  The W-blocked stencils (sf_dwconv.h) read every input element 13.5 times through the vector-memory
-// path; the LDS plane sweep of round 4 (sf_dwtile.h) fetches it once but keeps positions on the lanes: the 27 x 8 weights of a
-// lane then have to come out of LDS again for every plane (6 ds_read_b128 of weights beside 4 of data per 48 FMAs -- LDS-bound,
-// 36 us for a 15 us stream) and the staged tile is fp32 (48 KiB per plane).  Here
-//   * a lane owns FOUR CHANNELS (one 8-byte LDS word per position) and one row of the tile: its 27 x 4 fp32 weights are loop
-//     invariants in registers (the nn.Conv3d parameter itself, no rounding, no staging), read once per workgroup;
-//   * the 64 lanes of a wave are 8 rows x 8 channel quads and slide along W together: per output only the NEW column of the
-//     3 x 3 x 3 window is read (9 ds_read_b64 per 108 FMAs at stride 1, 18 at stride 2), the products are v_fma_mix (fp16 operand
-//     from the LDS word, fp32 weight, fp32 accumulate: no conversions); the row pitch of the staged tile is chosen so that the
-//     four rows of a 32-lane read group fall into four different 64-byte bank windows;
+// Why plane sweeps.  The W-blocked stencils (sf_dwconv.h) read every input element 13.5 times through the vector-memory path.  An
+// LDS plane sweep with the positions on the lanes (round 4) fetched it once, but the 27 x 8 weights of a lane then had to come out
+// of LDS again for every plane (6 ds_read_b128 of weights beside 4 of data per 48 FMAs -- LDS-bound, 36 us for a 15 us stream)
+// and the staged tile was fp32 (48 KiB per plane).  Here
+//   * a lane owns a few CHANNELS and one row of the tile: its 27 fp32 weights per channel are loop invariants in registers (the
+//     nn.Conv3d parameter itself, no rounding, no staging), read once per workgroup;
+//   * the lanes of a wave slide along W together: per output only the NEW column of the window is read;
 //   * planes stay fp16 in LDS (a whole 16 x 16 x 32-channel plane is 17 KiB) and travel global -> LDS directly
-//     (global_load_lds_dwordx4, zero line for the halo) into a ring of four slots: planes t-1, t, t+1 are read while t+2 lands; one
-//     raw barrier per plane, the wait for a plane's copies is a COUNTED vmcnt that leaves the output stores issued behind them in
-//     flight; the temporal halo planes -1 and T are zero copies through the same stream (no special cases in the loop).
-// Three bodies on this skeleton:
-//   MODE 0  forward (s = 1 | 2), and the stride-1 data gradient as the correlation with the mirrored weights;
-//   MODE 1  stride-2 data gradient: a lane owns a 2 x 2 block of dx and the 2 x 2 window of dy it depends on (9 of the 27 taps
-//           per position on average: no zero-upsampled products, the four parity classes are straight-line code);
-//   MODE 2  weight gradient: the same window as MODE 0 multiplied by the lane's dy word into 27 x 4 accumulators; the 32 lanes
-//           that share a channel quad are folded through LDS in a fixed order at the end, one partial row per workgroup
-//           (summed by sf_dwconv_wgrad_finalize_kernel).
-// BatchNorm partial sums (X3D) ride on MODE 0 as 8 more registers per lane.
+//     (global_load_lds_dwordx4, zero line for the halo) into a ring of slots: the planes being read stay resident while the next
+//     ones land; one raw barrier per plane, the wait for a plane's copies is a COUNTED vmcnt that leaves the output stores issued
+//     behind them in flight.
+// Three kernels on this skeleton:
+//   sf_dwsweep_kernel<1, 2, .>  stride-2 data gradient (four channels per lane, v_fma_mix);
+//   sf_dwrot_kernel             forward, stride-1 data gradient and weight gradient at every stride (rotating accumulators);
+//   sf_dwgap_dgrad_kernel       data gradient at strides >= 3 (no staging: an input position receives at most one (kh, kw) tap).
 #pragma once
 #include "sf_common.h"
 
 #define SF_DWS_LDS 81920                        // static LDS of a workgroup: two per CU
 #define SF_DWS_NR 4                             // ring slots of the staged operand
-#define SF_DWS_NRB 3                            // ring slots of dy (weight gradient)
 #define SF_DWS_MAXVPT 5                         // copy instructions per wave and plane (1 KiB each)
 #define SF_DWS_MAXVPTB 4
 
@@ -40,15 +32,16 @@ struct DwSweepParams {
     const f16* b; int ldb;              // weight gradient: dy
     f16* dst; int ldd;                  // y / dx
     const float* w;                     // [Cwreal][27] fp32 (the nn.Conv3d parameter)
-    float* part;                        // MODE 0: optional [rows][2][C] BatchNorm partial sums; MODE 2: [rows][27][C]
+    float* part;                        // forward: optional [rows][2][C] BatchNorm partial sums; data gradient: optional [rows][2][C]
+                                        // column sums of dx (slot 1 unspecified); weight gradient: [rows][27][C]
     int N, C, Cw, Cwreal, cls, T;
     int Ha, Wa, Hb, Wb, Hd, Wd;         // plane extents of a, b, dst
-    int Hit, Wit;                       // extents of the iterated space (outputs; MODE 1: 2 x 2 blocks of dx = positions of dy)
+    int Hit, Wit;                       // extents of the iterated space (outputs; stride-2 data gradient: 2 x 2 blocks of dx = positions of dy)
     int flip;                           // 1: taps mirrored (stride-1 data gradient)
     int TH, TW, tiles_h, tiles_w, nchunks;
     int RA, CA, RP, slotb, vpt;         // staged tile of a: rows, columns, row pitch and ring-slot size in bytes, copies per wave
     int RB, CBt, RPB, slotbB, vptB;     // staged tile of b
-    int ngrp, nseg, SL;                 // 8-row groups of the tile, column segments per group, columns per segment
+    int ngrp, nseg, SL;                 // row groups of the tile, column segments per group, columns per segment
     int nr;                             // sf_dwrot_kernel: ring slots of the staged operand (dy: nr - 1)
     int gs;                             // sf_dwrot_kernel<., 3, ...>: the convolution's stride (>= 3, windows do not overlap)
     // PAIR mode (csplit > 0; round 6): ONE launch for two convolutions of the same geometry on two tensors of csplit channels each
@@ -72,14 +65,12 @@ __device__ __forceinline__ float dws_half(uint32_t x, int e) {
     return (float)__builtin_bit_cast(f16, (uint16_t)(e ? x >> 16 : x & 0xffffu));
 #endif
 }
-// acc + x[E] * w and acc + x[EX] * y[EY] on v_fma_mix_f32 (fp16 operands picked out of the packed words by op_sel, fp32 accumulate:
-// no conversion instructions).  Written as asm: left to itself hipcc's SLP vectoriser turns the 108 FMAs of a step into
-// v_cvt_f32_f16 + v_pk_fma_f32 pairs -- twice the VALU issue slots (MI355X_MICROARCH.md: packed fp32 is no faster than two FMAs).
+// acc + x[E] * w on v_fma_mix_f32 (fp16 operand picked out of the packed word by op_sel, fp32 accumulate: no conversion
+// instructions).  Written as asm: left to itself hipcc's SLP vectoriser turns the FMAs of a step into v_cvt_f32_f16 + v_pk_fma_f32
+// pairs -- twice the VALU issue slots (MI355X_MICROARCH.md: packed fp32 is no faster than two FMAs).
 #if defined(SF_HOSTSIM) || defined(SF_ACT_BF16)
 template <int E>
 __device__ __forceinline__ float dws_fma_xw(uint32_t x, float w, float acc) { return __builtin_fmaf(dws_half(x, E), w, acc); }
-template <int EX, int EY>
-__device__ __forceinline__ float dws_fma_xy(uint32_t x, uint32_t y, float acc) { return __builtin_fmaf(dws_half(x, EX), dws_half(y, EY), acc); }
 #else
 template <int E>
 __device__ __forceinline__ float dws_fma_xw(uint32_t x, float w, float acc) {
@@ -87,27 +78,13 @@ __device__ __forceinline__ float dws_fma_xw(uint32_t x, float w, float acc) {
     else asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(acc) : "v"(x), "v"(w));
     return acc;
 }
-template <int EX, int EY>
-__device__ __forceinline__ float dws_fma_xy(uint32_t x, uint32_t y, float acc) {
-    if constexpr (EX == 0 && EY == 0) asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x), "v"(y));
-    else if constexpr (EX == 1 && EY == 0) asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x), "v"(y));
-    else if constexpr (EX == 0 && EY == 1) asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x), "v"(y));
-    else asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x), "v"(y));
-    return acc;
-}
 #endif
-// the four channels of a word pair against four fp32 weights / against the four channels of another pair
+// the four channels of a word pair against four fp32 weights
 __device__ __forceinline__ void dws_fma4_w(const dws_w2& x, const float (&w)[4], float (&acc)[4]) {
     acc[0] = dws_fma_xw<0>(x.x, w[0], acc[0]);
     acc[1] = dws_fma_xw<1>(x.x, w[1], acc[1]);
     acc[2] = dws_fma_xw<0>(x.y, w[2], acc[2]);
     acc[3] = dws_fma_xw<1>(x.y, w[3], acc[3]);
-}
-__device__ __forceinline__ void dws_fma4_y(const dws_w2& x, const dws_w2& y, float (&acc)[4]) {
-    acc[0] = dws_fma_xy<0, 0>(x.x, y.x, acc[0]);
-    acc[1] = dws_fma_xy<1, 1>(x.x, y.x, acc[1]);
-    acc[2] = dws_fma_xy<0, 0>(x.y, y.y, acc[2]);
-    acc[3] = dws_fma_xy<1, 1>(x.y, y.y, acc[3]);
 }
 
 // wait until this wave's copies are done while up to `keep` (wave-uniform) younger stores stay in flight
@@ -118,8 +95,15 @@ __device__ __forceinline__ void dws_wait_copies(int keep) {
     else SF_WAIT_VMEM_N(0);
 }
 
+// Stride-2 data gradient.  A lane owns FOUR CHANNELS (one 8-byte LDS word per position: the 27 x 4 weights are registers) and one
+// row of 2 x 2 blocks of dx; the 64 lanes of a wave are 8 block rows x 8 channel quads.  A block depends on the 2 x 2 window of dy
+// at the block's own position (9 of the 27 taps per position on average: no zero-upsampled products, the four parity classes are
+// straight-line code); the staged tile is dy, ring of four slots: planes t-1, t, t+1 are read while t+2 lands, the temporal halo
+// planes -1 and T are zero copies through the same stream.  STATS: the column sums of dx ride along as 4 more registers per lane.
+// (MODE and S are fixed at 1 and 2: they name the kernel as the round-6 tables and traces do.)
 template <int MODE, int S, bool STATS>
 __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams p) {
+    static_assert(MODE == 1 && S == 2, "sf_dwsweep_kernel: stride-2 data gradient only");
     __shared__ __attribute__((aligned(1024))) char smem[SF_DWS_LDS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -139,13 +123,12 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
     }
     const int cq = (p.C - c0) >= 32 ? 8 : (p.C - c0) >> 2;      // channel quads of this chunk
     const bool qok = q < cq;
-    const int r0 = th * p.TH, q0 = tw * p.TW;                   // tile origin in the iterated space
-    const int ar0 = MODE == 1 ? r0 : r0 * S - 1, ac0 = MODE == 1 ? q0 : q0 * S - 1;     // origin of the staged tile of a
+    const int r0 = th * p.TH, q0 = tw * p.TW;                   // tile origin in the iterated space (= origin of the staged dy tile)
     const f16* const zline = reinterpret_cast<const f16*>(sf_zero_line);
 
     // ---- weights of the lane's four channels (channel c uses weight row c % Cw; rows >= Cwreal are padding)
-    float wr[MODE == 2 ? 1 : 27][4];
-    if constexpr (MODE != 2) {
+    float wr[27][4];
+    {
         const int cw = (c0 + 4 * (qok ? q : 0)) % p.Cw;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -159,7 +142,7 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
         }
     }
 
-    // ---- copy maps: instruction u of this wave fills bytes [(4u + wave) KiB, +1 KiB) of a ring slot, 16 bytes per lane
+    // ---- copy map: instruction u of this wave fills bytes [(4u + wave) KiB, +1 KiB) of a ring slot, 16 bytes per lane
     const int64_t Sa = (int64_t)p.T * p.Ha * p.Wa + p.cls;
     const f16* const a_n = p.a + ((int64_t)n * Sa + p.cls) * p.lda + c0;
     const int64_t planeA = (int64_t)p.Ha * p.Wa * p.lda;
@@ -172,7 +155,7 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
             uint32_t i, rem;
             fd_divmod(o, p.fdRP, i, rem);
             const int j = (int)(rem >> 6), sub = (int)(rem & 63);
-            const int gr = ar0 + (int)i, gc = ac0 + j;
+            const int gr = r0 + (int)i, gc = q0 + j;
             if ((int)i < p.RA && j < p.CA && (sub >> 3) < cq && (unsigned)gr < (unsigned)p.Ha && (unsigned)gc < (unsigned)p.Wa)
                 aoff[u] = (gr * p.Wa + gc) * p.lda + (sub >> 1);
         }
@@ -188,59 +171,25 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
                 SF_GLOBAL_LOAD_LDS16_ASM(g, slot + u * 4096);
             }
     };
-    // dy planes of the weight gradient: [TH rows][TW columns][64 B], no halo; rows / columns beyond the plane are zeros
-    char* const smemB = smem + SF_DWS_NR * p.slotb;
-    const int64_t Sb = (int64_t)p.T * p.Hb * p.Wb + p.cls;
-    const f16* const b_n = MODE == 2 ? p.b + ((int64_t)n * Sb + p.cls) * p.ldb + c0 : nullptr;
-    const int64_t planeB = (int64_t)p.Hb * p.Wb * p.ldb;
-    int boff[MODE == 2 ? SF_DWS_MAXVPTB : 1];
-    if constexpr (MODE == 2) {
-#pragma unroll
-        for (int u = 0; u < SF_DWS_MAXVPTB; ++u) {
-            boff[u] = -1;
-            if (u < p.vptB && (u * 4 + wave) * 1024 < p.slotbB) {
-                const uint32_t o = (uint32_t)(((u * 4 + wave) * 64 + lane) * 16);
-                uint32_t i, rem;
-                fd_divmod(o, p.fdRPB, i, rem);
-                const int j = (int)(rem >> 6), sub = (int)(rem & 63);
-                const int gr = r0 + (int)i, gc = q0 + j;
-                if ((int)i < p.RB && j < p.CBt && (sub >> 3) < cq && gr < p.Hb && gc < p.Wb) boff[u] = (gr * p.Wb + gc) * p.ldb + (sub >> 1);
-            }
-        }
-    }
-    auto issue_b = [&](int t) {
-        if constexpr (MODE == 2) {
-            const f16* base = b_n + (int64_t)t * planeB;
-            char* slot = smemB + (t % SF_DWS_NRB) * p.slotbB + wave * 1024;
-#pragma unroll
-            for (int u = 0; u < SF_DWS_MAXVPTB; ++u)
-                if (u < p.vptB && (u * 4 + wave) * 1024 < p.slotbB) {
-                    const f16* g = boff[u] >= 0 ? base + boff[u] : zline;
-                    SF_GLOBAL_LOAD_LDS16_ASM(g, slot + u * 4096);
-                }
-        }
-    };
 
     // ---- destination
     const int64_t Sd = (int64_t)p.T * p.Hd * p.Wd + p.cls;
-    f16* const dst_n = MODE == 2 ? nullptr : p.dst + ((int64_t)n * Sd + p.cls) * p.ldd + c0 + 4 * q;
-    if (MODE != 2 && p.cls && th == 0 && tw == 0 && tid < (cq >> 1))      // the cls row passes through
+    f16* const dst_n = p.dst + ((int64_t)n * Sd + p.cls) * p.ldd + c0 + 4 * q;
+    if (p.cls && th == 0 && tw == 0 && tid < (cq >> 1))      // the cls row passes through
         st16(p.dst + (int64_t)n * Sd * p.ldd + c0 + tid * 8, ld16(p.a + (int64_t)n * Sa * p.lda + c0 + tid * 8));
 
     const int ntask = p.ngrp * p.nseg;
     // output stores this wave issues per plane (>= is enough: the counted wait may only under-estimate)
     int nst = 0;
-    if constexpr (MODE != 2) {
-        for (int k = wave; k < ntask; k += 4) {
-            uint32_t g, sg;
-            fd_divmod((uint32_t)k, p.fdSeg, g, sg);
-            int ce = (int)sg * p.SL + p.SL;
-            if (ce > p.TW) ce = p.TW;
-            if (q0 + ce > p.Wit) ce = p.Wit - q0;
-            const int len = ce - (int)sg * p.SL;
-            // (only the stores that are certain: a group whose first row is inside the tile, one store per step)
-            if (len > 0 && (int)g * 8 < p.TH && r0 + (int)g * 8 < p.Hit) nst += len;
-        }
+    for (int k = wave; k < ntask; k += 4) {
+        uint32_t g, sg;
+        fd_divmod((uint32_t)k, p.fdSeg, g, sg);
+        int ce = (int)sg * p.SL + p.SL;
+        if (ce > p.TW) ce = p.TW;
+        if (q0 + ce > p.Wit) ce = p.Wit - q0;
+        const int len = ce - (int)sg * p.SL;
+        // (only the stores that are certain: a group whose first row is inside the tile, one store per step)
+        if (len > 0 && (int)g * 8 < p.TH && r0 + (int)g * 8 < p.Hit) nst += len;
     }
 
     float ssum[STATS ? 4 : 1], ssq[STATS ? 4 : 1];
@@ -248,27 +197,10 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
 #pragma unroll
         for (int e = 0; e < 4; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; }
     }
-    float wacc[MODE == 2 ? 27 : 1][4];
-    if constexpr (MODE == 2) {
-#pragma unroll
-        for (int tap = 0; tap < 27; ++tap)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) wacc[tap][e] = 0.f;
-    }
-
-    // ---- column of the window: the 3 (planes) x 3 (rows) words of staged column j; base[] = per-plane lane addresses
-    auto load_col = [&](dws_w2 (&X)[3][3], const int (&base)[3], int j) {
-#pragma unroll
-        for (int kt = 0; kt < 3; ++kt)
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh) X[kt][kh] = dws_ld(smem, base[kt] + kh * p.RP + j * 64);
-    };
 
     issue_a(-1);
     issue_a(0);
     issue_a(1);
-    issue_b(0);
-    if (p.T > 1) issue_b(1);
 
     for (int t = 0; t < p.T; ++t) {
         // planes <= t + 1 were issued before the previous plane's stores: retire them, keep the stores in flight
@@ -276,7 +208,6 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
         else dws_wait_copies(nst);
         SF_BARRIER_KEEP_VMEM();             // copies of every wave visible; everyone is done with plane t - 2
         if (t + 2 <= p.T) issue_a(t + 2);
-        if (MODE == 2 && t + 2 < p.T) issue_b(t + 2);
 
         int pbase[3];
 #pragma unroll
@@ -294,161 +225,78 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
             const int rr = rok ? r : 0, qq = qok ? q : 0;
             const bool lok = rok && qok;
 
-            if constexpr (MODE == 0 || MODE == 2) {
-                int base[3];
+            // lane = block row a = r (dx rows 2a, 2a + 1), columns b = c (dx columns 2b, 2b + 1); the staged tile holds dy rows
+            // r0 .. r0 + TH and columns q0 .. q0 + TW (zeros beyond the plane).  dx plane t takes dy plane t + 1 - kt.
+            int base[3];
 #pragma unroll
-                for (int kt = 0; kt < 3; ++kt) base[kt] = pbase[kt] + rr * S * p.RP + qq * 8;
-                f16* drow = nullptr;
-                const char* brow = nullptr;
-                if constexpr (MODE == 0) drow = dst_n + ((int64_t)(t * p.Hd + r0 + r) * p.Wd + q0) * p.ldd;
-                else brow = smemB + (t % SF_DWS_NRB) * p.slotbB + rr * p.RPB + qq * 8;
-                dws_w2 X0[3][3], X1[3][3], X2[3][3];
-                // one output column: A, B, C hold staged columns c*S, c*S + 1, c*S + 2
-                auto body = [&](const dws_w2 (&A)[3][3], const dws_w2 (&B)[3][3], const dws_w2 (&Cc)[3][3], int c) {
-                    if constexpr (MODE == 0) {
-                        // column by column (kw outer): the window slot of kw = 0 is dead after its 36 FMAs
-                        float a0[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int pl = 0; pl < 3; ++pl) base[pl] = pbase[pl] + rr * p.RP + qq * 8;
+            const int h0 = 2 * (r0 + r), w00 = 2 * q0;
+            f16* drow = dst_n + ((int64_t)(t * p.Hd + h0) * p.Wd + w00) * p.ldd;
+            const bool row1 = h0 + 1 < p.Hd;
+            dws_w2 D0[3][2], D1[3][2];
+            auto load2 = [&](dws_w2 (&D)[3][2], int j) {
 #pragma unroll
-                        for (int kw = 0; kw < 3; ++kw)
+                for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-                            for (int kt = 0; kt < 3; ++kt)
+                    for (int i = 0; i < 2; ++i) D[pl][i] = dws_ld(smem, base[pl] + i * p.RP + j * 64);
+            };
+            auto body = [&](const dws_w2 (&L)[3][2], const dws_w2 (&R)[3][2], int c) {
+                float o00[4], o01[4], o10[4], o11[4];
 #pragma unroll
-                                for (int kh = 0; kh < 3; ++kh) {
-                                    const dws_w2& x = kw == 0 ? A[kt][kh] : kw == 1 ? B[kt][kh] : Cc[kt][kh];
-                                    dws_fma4_w(x, wr[(kt * 3 + kh) * 3 + kw], a0);
-                                }
-                        dws_x4 o;
+                for (int e = 0; e < 4; ++e) { o00[e] = 0.f; o01[e] = 0.f; o10[e] = 0.f; o11[e] = 0.f; }
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) {
+                    const int k9 = (2 - pl) * 9;          // kt = 2 - pl; taps (kh, kw) of that temporal slice
+                    const dws_w2 &d00 = L[pl][0], &d01 = R[pl][0], &d10 = L[pl][1], &d11 = R[pl][1];
+                    dws_fma4_w(d00, wr[k9 + 4], o00);
+                    dws_fma4_w(d01, wr[k9 + 3], o01);
+                    dws_fma4_w(d00, wr[k9 + 5], o01);
+                    dws_fma4_w(d10, wr[k9 + 1], o10);
+                    dws_fma4_w(d00, wr[k9 + 7], o10);
+                    dws_fma4_w(d11, wr[k9 + 0], o11);
+                    dws_fma4_w(d10, wr[k9 + 2], o11);
+                    dws_fma4_w(d01, wr[k9 + 6], o11);
+                    dws_fma4_w(d00, wr[k9 + 8], o11);
+                }
+                dws_x4 v00, v01, v10, v11;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { v00[e] = (f16)o00[e]; v01[e] = (f16)o01[e]; v10[e] = (f16)o10[e]; v11[e] = (f16)o11[e]; }
+                const bool col1 = w00 + 2 * c + 1 < p.Wd;
+                f16* d = drow + (int64_t)(2 * c) * p.ldd;
+                if (lok) {
+                    *reinterpret_cast<dws_x4*>(d) = v00;
+                    if (col1) *reinterpret_cast<dws_x4*>(d + p.ldd) = v01;
+                    if (row1) {
+                        f16* d1 = d + (int64_t)p.Wd * p.ldd;
+                        *reinterpret_cast<dws_x4*>(d1) = v10;
+                        if (col1) *reinterpret_cast<dws_x4*>(d1 + p.ldd) = v11;
+                    }
+                    if constexpr (STATS) {          // column sums of dx (the bias gradient of the Linear that produced x)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float v = a0[e];
-                            o[e] = (f16)v;
-                            if constexpr (STATS) {
-                                if (lok) { ssum[e] += v; ssq[e] += v * v; }
-                            }
-                        }
-                        if (lok) *reinterpret_cast<dws_x4*>(drow + (int64_t)c * p.ldd) = o;
-                    } else {
-                        dws_w2 d = dws_ld(brow, c * 64);
-                        if (!lok) d = (dws_w2){0u, 0u};
-#pragma unroll
-                        for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-                            for (int kt = 0; kt < 3; ++kt)
-#pragma unroll
-                                for (int kh = 0; kh < 3; ++kh) {
-                                    const dws_w2& x = kw == 0 ? A[kt][kh] : kw == 1 ? B[kt][kh] : Cc[kt][kh];
-                                    dws_fma4_y(x, d, wacc[(kt * 3 + kh) * 3 + kw]);
-                                }
-                    }
-                };
-                if constexpr (S == 1) {
-                    // window (A, B, C) = columns (c, c+1, c+2); the next output needs (B, C, new)
-                    load_col(X0, base, cs);
-                    load_col(X1, base, cs + 1);
-                    for (int c = cs; c < ce; c += 3) {
-                        load_col(X2, base, c + 2);
-                        body(X0, X1, X2, c);
-                        if (c + 1 < ce) {
-                            load_col(X0, base, c + 3);
-                            body(X1, X2, X0, c + 1);
-                        }
-                        if (c + 2 < ce) {
-                            load_col(X1, base, c + 4);
-                            body(X2, X0, X1, c + 2);
-                        }
-                    }
-                } else {
-                    // window (A, B, C) = columns (2c, 2c+1, 2c+2); the next output needs (C, new, new)
-                    load_col(X0, base, 2 * cs);
-                    for (int c = cs; c < ce; c += 3) {
-                        load_col(X1, base, 2 * c + 1);
-                        load_col(X2, base, 2 * c + 2);
-                        body(X0, X1, X2, c);
-                        if (c + 1 < ce) {
-                            load_col(X0, base, 2 * c + 3);
-                            load_col(X1, base, 2 * c + 4);
-                            body(X2, X0, X1, c + 1);
-                        }
-                        if (c + 2 < ce) {
-                            load_col(X2, base, 2 * c + 5);
-                            load_col(X0, base, 2 * c + 6);
-                            body(X1, X2, X0, c + 2);
+                            float a = o00[e];
+                            if (col1) a += o01[e];
+                            if (row1) { a += o10[e]; if (col1) a += o11[e]; }
+                            ssum[e] += a;
                         }
                     }
                 }
-            } else {
-                // ---- MODE 1: lane = block row a = r (dx rows 2a, 2a + 1), columns b = c (dx columns 2b, 2b + 1); the staged tile
-                // holds dy rows r0 .. r0 + TH and columns q0 .. q0 + TW (zeros beyond the plane).  dx plane t takes dy plane t + 1 - kt.
-                int base[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) base[pl] = pbase[pl] + rr * p.RP + qq * 8;
-                const int h0 = 2 * (r0 + r), w00 = 2 * q0;
-                f16* drow = dst_n + ((int64_t)(t * p.Hd + h0) * p.Wd + w00) * p.ldd;
-                const bool row1 = h0 + 1 < p.Hd;
-                dws_w2 D0[3][2], D1[3][2];
-                auto load2 = [&](dws_w2 (&D)[3][2], int j) {
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) D[pl][i] = dws_ld(smem, base[pl] + i * p.RP + j * 64);
-                };
-                auto body = [&](const dws_w2 (&L)[3][2], const dws_w2 (&R)[3][2], int c) {
-                    float o00[4], o01[4], o10[4], o11[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { o00[e] = 0.f; o01[e] = 0.f; o10[e] = 0.f; o11[e] = 0.f; }
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) {
-                        const int k9 = (2 - pl) * 9;          // kt = 2 - pl; taps (kh, kw) of that temporal slice
-                        const dws_w2 &d00 = L[pl][0], &d01 = R[pl][0], &d10 = L[pl][1], &d11 = R[pl][1];
-                        dws_fma4_w(d00, wr[k9 + 4], o00);
-                        dws_fma4_w(d01, wr[k9 + 3], o01);
-                        dws_fma4_w(d00, wr[k9 + 5], o01);
-                        dws_fma4_w(d10, wr[k9 + 1], o10);
-                        dws_fma4_w(d00, wr[k9 + 7], o10);
-                        dws_fma4_w(d11, wr[k9 + 0], o11);
-                        dws_fma4_w(d10, wr[k9 + 2], o11);
-                        dws_fma4_w(d01, wr[k9 + 6], o11);
-                        dws_fma4_w(d00, wr[k9 + 8], o11);
-                    }
-                    dws_x4 v00, v01, v10, v11;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v00[e] = (f16)o00[e]; v01[e] = (f16)o01[e]; v10[e] = (f16)o10[e]; v11[e] = (f16)o11[e]; }
-                    const bool col1 = w00 + 2 * c + 1 < p.Wd;
-                    f16* d = drow + (int64_t)(2 * c) * p.ldd;
-                    if (lok) {
-                        *reinterpret_cast<dws_x4*>(d) = v00;
-                        if (col1) *reinterpret_cast<dws_x4*>(d + p.ldd) = v01;
-                        if (row1) {
-                            f16* d1 = d + (int64_t)p.Wd * p.ldd;
-                            *reinterpret_cast<dws_x4*>(d1) = v10;
-                            if (col1) *reinterpret_cast<dws_x4*>(d1 + p.ldd) = v11;
-                        }
-                        if constexpr (STATS) {          // column sums of dx (the bias gradient of the Linear that produced x)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                float a = o00[e];
-                                if (col1) a += o01[e];
-                                if (row1) { a += o10[e]; if (col1) a += o11[e]; }
-                                ssum[e] += a;
-                            }
-                        }
-                    }
-                };
-                load2(D0, cs);
-                for (int c = cs; c < ce; c += 2) {
-                    load2(D1, c + 1);
-                    body(D0, D1, c);
-                    if (c + 1 < ce) {
-                        load2(D0, c + 2);
-                        body(D1, D0, c + 1);
-                    }
+            };
+            load2(D0, cs);
+            for (int c = cs; c < ce; c += 2) {
+                load2(D1, c + 1);
+                body(D0, D1, c);
+                if (c + 1 < ce) {
+                    load2(D0, c + 2);
+                    body(D1, D0, c + 1);
                 }
             }
         }
     }
 
-    // ---- epilogues: fold the 32 lanes (8 row slots x 4 waves) that share a channel quad, fixed order
-    if constexpr (MODE != 2 && STATS) {
+    // ---- epilogue: fold the 32 lanes (8 row slots x 4 waves) that share a channel quad, fixed order (slot 1 of the table is
+    // written, not specified)
+    if constexpr (STATS) {
         __syncthreads();
         float* red = reinterpret_cast<float*>(smem);
 #pragma unroll
@@ -470,26 +318,6 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
             if ((ch >> 2) < cq) p.part[(prow * 2 + st) * cpw + cpart + ch] = acc;
         }
     }
-    if constexpr (MODE == 2) {
-        float* red = reinterpret_cast<float*>(smem);
-        const int64_t prow = ((int64_t)n * p.tiles_h + th) * p.tiles_w + tw;
-#pragma unroll
-        for (int kt = 0; kt < 3; ++kt) {
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 9; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) red[tid * 36 + i * 4 + e] = wacc[kt * 9 + i][e];
-            __syncthreads();
-            for (int o = tid; o < 9 * 32; o += SF_THREADS) {
-                const int i = o >> 5, ch = o & 31;
-                float acc = 0.f;
-                for (int wv = 0; wv < 4; ++wv)
-                    for (int r = 0; r < 8; ++r) acc += red[(wv * 64 + r * 8 + (ch >> 2)) * 36 + i * 4 + (ch & 3)];
-                if ((ch >> 2) < cq) p.part[(prow * 27 + kt * 9 + i) * cpw + cpart + ch] = acc;
-            }
-        }
-    }
 }
 
 // ========================================================================================================================
@@ -497,8 +325,9 @@ __global__ __launch_bounds__(SF_THREADS, 2) void sf_dwsweep_kernel(DwSweepParams
 //
 // Measured on MI355X (tools/ubench/valu_rate.hip, profiles/r6_v3_valu_rate.txt): EVERY VALU wave-instruction issues in ~4 cycles per
 // SIMD -- v_fma_f32, v_fma_mix_f32, v_cvt_f32_f16 alike -- and v_pk_fma_f32 does TWO fp32 FMAs in ~4.6.  The 108 v_fma_mix per
-// step of sf_dwsweep_kernel are therefore already the floor of that body (PMC: 7 900 VALU instructions per wave at 4 cycles each,
-// two waves per SIMD).  This body halves the instruction count:
+// step of the first form's forward (four channels per lane, the body sf_dwsweep_kernel keeps for the stride-2 data gradient) were
+// therefore already the floor of that body (PMC: 7 900 VALU instructions per wave at 4 cycles each, two waves per SIMD).  This body
+// halves the instruction count:
 //   * a lane owns a channel PAIR (one 32-bit LDS word per position), one row and a run of SL output columns, and keeps the
 //     accumulators of THREE output planes (t-1, t, t+1) for the whole run in registers (3 x SL x 2 fp32);
 //   * the sweep visits one INPUT plane per iteration: every word of the lane's 3 x (SL + 2) window is read once, converted once

@@ -43,8 +43,8 @@ def test_dwconv_tokens(gpu):
     tc.check_dwconv(gpu, 2, 1, 56, (4, 28, 28), (3, 3, 3), (1, 1, 1), cls=0)
     tc.check_dwconv(gpu, 2, 1, 56, (4, 56, 56), (3, 3, 3), (1, 2, 2), cls=0)
     tc.check_dwconv(gpu, 1, 1, 432, (4, 8, 8), (3, 3, 3), (1, 1, 1), cls=0)
-    # MViTv2-S stage 3 / 4 production planes (VERDICT r4 test gap): 14-wide, stride 1 (q pooling: sf_dwtile_kernel forward + data
-    # gradient, sf_dwtile_wgrad_kernel<1, ...>) and stride 2 at C = 384 (4 heads) and C = 768 (8 heads)
+    # MViTv2-S stage 3 / 4 production planes (VERDICT r4 test gap): 14-wide, stride 1 (q pooling: sf_dwrot_kernel forward, data
+    # gradient and weight gradient) and stride 2 at C = 384 (4 heads) and C = 768 (8 heads)
     tc.check_dwconv(gpu, 2, 4, 96, (4, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)
     tc.check_dwconv(gpu, 1, 8, 96, (4, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)
     tc.check_dwconv(gpu, 2, 4, 96, (8, 14, 14), (3, 3, 3), (1, 2, 2), cls=1)
@@ -102,20 +102,18 @@ def test_dwconv_ring_sweep(gpu, monkeypatch):
         tc.check_dwconv(gpu, 1, 1, 40, (3, 13, 21), (3, 3, 3), (1, 2, 2), cls=0)
     for k in ("SF_DWR_SL", "SF_DWR_NGRP", "SF_DWR_NSEG"):
         monkeypatch.delenv(k)
-    monkeypatch.setenv("SF_DW_ROT", "0")                                         # the four-channel v_fma_mix body, forced tilings
-    monkeypatch.setenv("SF_DWS_TH", "5")
-    monkeypatch.setenv("SF_DWS_TW", "6")
-    tc.check_dwconv(gpu, 2, 4, 96, (3, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)
+    monkeypatch.setenv("SF_DWS_TH", "5")                                         # stride-2 data gradient (sf_dwsweep_kernel<1, 2, .>),
+    monkeypatch.setenv("SF_DWS_TW", "6")                                         # forced tilings
     tc.check_dwconv(gpu, 2, 4, 96, (3, 14, 14), (3, 3, 3), (1, 2, 2), cls=1)
     monkeypatch.setenv("SF_DWS_TH", "11")
     monkeypatch.setenv("SF_DWS_TW", "20")
     monkeypatch.setenv("SF_DWS_NSEG", "3")
-    tc.check_dwconv(gpu, 1, 1, 40, (2, 12, 20), (3, 3, 3), (1, 1, 1), cls=1)
     tc.check_dwconv(gpu, 1, 1, 40, (1, 13, 21), (3, 3, 3), (1, 2, 2), cls=0)
+    tc.check_dwconv(gpu, 1, 1, 40, (2, 24, 21), (3, 3, 3), (1, 2, 2), cls=1)     # Ho = 12: two row groups, the second partial
 
 
 def test_dwconv_tokens_stencils(gpu, monkeypatch):
-    """The stencils and the round-4 LDS plane sweep the ring sweep replaced (still the fallback for other geometries)."""
+    """The W-blocked stencils the plane sweeps replaced for 3x3x3, stride <= 2 (still the path of other windows)."""
     monkeypatch.setenv("SF_DW_SWEEP", "0")
     tc.check_dwconv(gpu, 2, 2, 96, (4, 14, 14), (3, 3, 3), (1, 2, 2), cls=1)
     tc.check_dwconv(gpu, 2, 4, 96, (4, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)

@@ -102,25 +102,23 @@ def _dwconv_tokens(sim):
 
 
 def test_dwconv_ring_sweep(sim, monkeypatch):
-    """Ring-buffered plane sweep with the channels on the lanes (sf_dwsweep.h, round 6): forward (stride 1 | 2, with and without the
-    BatchNorm partial sums), both data gradients, the weight gradient; whole and ragged tiles in H and W, several row groups and
-    column segments per wave, 8- / 16- / 24-channel tail chunks, heads sharing a weight, T = 1, odd extents.  (SF_DW_ROT=0: the
-    four-channel v_fma_mix body; by default only its stride-2 data gradient is dispatched.)"""
-    monkeypatch.setenv("SF_DW_ROT", "0")
+    """Plane sweeps at MViT / X3D geometries (sf_dwsweep.h): forward (stride 1 | 2, with and without the BatchNorm partial sums),
+    both data gradients, the weight gradient; 8- / 16- / 24-channel tail chunks, heads sharing a weight, T = 1, odd extents.  The
+    stride-2 data gradient (sf_dwsweep_kernel<1, 2, .>) also under forced tilings: whole and ragged tiles in H and W, several row
+    groups and column segments per wave."""
     tc.check_dwconv(sim, 1, 1, 32, (2, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)     # MViT stage-3 plane: two row groups x two segments
     tc.check_dwconv(sim, 1, 1, 64, (3, 14, 14), (3, 3, 3), (1, 2, 2), cls=1)     # 14 -> 7, two chunks
     tc.check_dwconv(sim, 1, 2, 32, (2, 7, 9), (3, 3, 3), (1, 2, 2), cls=0)       # odd extents: 7x9 -> 4x5, no cls (partial sums ride)
     tc.check_dwconv(sim, 1, 1, 56, (2, 9, 10), (3, 3, 3), (1, 1, 1), cls=0)      # X3D width 54 -> 56: a 32- and a 24-channel chunk
     tc.check_dwconv(sim, 1, 1, 40, (1, 6, 11), (3, 3, 3), (1, 2, 2), cls=0)      # 8-channel tail chunk, T = 1
-    monkeypatch.setenv("SF_DWS_TH", "5")                                         # ragged row tiles (14 = 5 + 5 + 4), ...
-    monkeypatch.setenv("SF_DWS_TW", "6")                                         # ... ragged column tiles (14 = 6 + 6 + 2)
-    tc.check_dwconv(sim, 1, 1, 32, (3, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)
+    monkeypatch.setenv("SF_DWS_TH", "5")                                         # ragged row tiles (7 = 5 + 2), ...
+    monkeypatch.setenv("SF_DWS_TW", "6")                                         # ... ragged column tiles (7 = 6 + 1)
     tc.check_dwconv(sim, 1, 1, 32, (2, 14, 14), (3, 3, 3), (1, 2, 2), cls=0)
-    monkeypatch.setenv("SF_DWS_TH", "11")                                        # two row groups, the second one partial
-    monkeypatch.setenv("SF_DWS_TW", "20")
-    monkeypatch.setenv("SF_DWS_NSEG", "3")                                       # segments of 7, 7, 6 columns (window rotation tails)
-    tc.check_dwconv(sim, 1, 1, 16, (2, 12, 20), (3, 3, 3), (1, 1, 1), cls=1)
-    monkeypatch.setenv("SF_DWS_NSEG", "1")                                       # one segment: tasks < waves
+    monkeypatch.setenv("SF_DWS_TH", "11")                                        # Ho = 12: two row groups, the second one partial,
+    monkeypatch.setenv("SF_DWS_TW", "20")                                        # and a one-row second tile
+    monkeypatch.setenv("SF_DWS_NSEG", "3")                                       # segments of 4, 4, 2 columns
+    tc.check_dwconv(sim, 1, 1, 16, (2, 24, 20), (3, 3, 3), (1, 2, 2), cls=1)
+    monkeypatch.setenv("SF_DWS_NSEG", "1")                                       # Ho = 6: one group, one segment (tasks < waves)
     tc.check_dwconv(sim, 1, 1, 16, (2, 12, 20), (3, 3, 3), (1, 2, 2), cls=1)
 
 
@@ -146,31 +144,10 @@ def test_dwconv_rotating_sweep(sim, monkeypatch):
     tc.check_dwconv(sim, 1, 1, 24, (4, 10, 13), (3, 3, 3), (1, 3, 3), cls=0)
     monkeypatch.setenv("SF_DWR_SL", "7")
     tc.check_dwconv(sim, 1, 1, 32, (2, 30, 30), (3, 3, 3), (1, 4, 4), cls=1)
-
-
-def test_dwconv_tiled_plane_sweep(sim, monkeypatch):
-    """LDS-tiled plane sweep (sf_dwtile.h): 32-channel chunks, strides 1 and 2 (forward, data gradient incl. the zero-upsampled
-    stride-2 form, weight gradient in its three LDS classes), partial last row tiles, odd extents, 1 / 2 / 4 positions per thread."""
-    monkeypatch.setenv("SF_DW_SWEEP", "0")      # the round-6 ring sweep would take every one of these geometries
-    monkeypatch.setenv("SF_DW_TILED", "2")      # also the stride-2 forms (the library's statics are read on first use: the
-    # fixture loads a fresh library handle per test, the env is read again)
-    tc.check_dwconv(sim, 2, 2, 32, (3, 6, 6), (3, 3, 3), (1, 1, 1), cls=1)       # one tile, NP = 1
-    tc.check_dwconv(sim, 1, 1, 32, (2, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)     # MViT stage-3 plane, NP = 2 / 4
-    tc.check_dwconv(sim, 1, 1, 64, (3, 14, 14), (3, 3, 3), (1, 2, 2), cls=1)     # 14 -> 7, two chunks
-    tc.check_dwconv(sim, 1, 2, 32, (2, 7, 9), (3, 3, 3), (1, 2, 2), cls=0)       # odd extents: 7x9 -> 4x5, no cls
-    tc.check_dwconv(sim, 1, 1, 32, (1, 5, 30), (3, 3, 3), (1, 1, 1), cls=1)      # wide rows: several row tiles, T = 1
+    monkeypatch.delenv("SF_DWR_SL")
+    tc.check_dwconv(sim, 2, 2, 32, (3, 6, 6), (3, 3, 3), (1, 1, 1), cls=1)       # one tile, two samples x two heads
+    tc.check_dwconv(sim, 1, 1, 32, (1, 5, 30), (3, 3, 3), (1, 1, 1), cls=1)      # wide rows: several column tiles, T = 1
     tc.check_dwconv(sim, 1, 1, 96, (4, 12, 12), (3, 3, 3), (1, 2, 2), cls=1)     # head width 96 (three chunks of one weight group)
-    monkeypatch.setenv("SF_DWT_TH", "13")                                        # weight gradient: the 85 KiB class (182 positions
-    tc.check_dwconv(sim, 1, 1, 32, (2, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)     # per dy slot), partial second tile
-    monkeypatch.delenv("SF_DWT_TH")
-    monkeypatch.setenv("SF_DW_WGRAD_TILED", "0")                                 # ... and the stencil it replaces, same case
-    tc.check_dwconv(sim, 1, 1, 32, (2, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)
-    monkeypatch.delenv("SF_DW_WGRAD_TILED")
-    monkeypatch.setenv("SF_DWT_TH", "7")                                         # 98 positions per tile: 2 per thread
-    tc.check_dwconv(sim, 1, 1, 32, (2, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)
-    monkeypatch.setenv("SF_DWT_TH", "14")                                        # 196 positions: 4 per thread (3 rounds up)
-    tc.check_dwconv(sim, 1, 1, 32, (2, 14, 14), (3, 3, 3), (1, 1, 1), cls=1)
-    tc.check_dwconv(sim, 1, 1, 32, (2, 14, 14), (3, 3, 3), (1, 2, 2), cls=1)
 
 
 def test_token_pool(sim):
