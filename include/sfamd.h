@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 23
+#define SF_ABI_VERSION 24
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -464,6 +464,29 @@ int sf_flat_sgd(float* param, const float* grad, float* mom, const void* segs, c
 int sf_flat_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const void* segs, const int32_t* blk_seg,
                   const int32_t* blk_off, int32_t nblocks, const float* ctl, const float* lr, const float* wd, int32_t ngroups,
                   float clip_val, float beta1, float beta2, float eps, sf_stream_t stream);
+/* Table-driven update (ABI 24): sf_flat_sgd / sf_flat_adamw with the per-group hyper-parameters in DEVICE memory and no cap on
+ * the number of groups -- slowfast/models/optimizer.py:146-237 (get_param_groups makes 2 * (MVIT.DEPTH + 2) groups and set_lr
+ * rescales every one of them each iteration; a captured graph reads the table on replay, so the schedule survives capture).
+ * hyper: [ngroups][4] fp32 {lr, weight_decay, lars_group (0 / 1), reserved}, 16-byte aligned, indexed by the segment's group.
+ * trust: NULL, or [nseg] fp32 written by sf_flat_lars_trust; with it the LARS wrapper of optimizer.py:262-359 applies
+ * (trust_coefficient mode, clip=False): a parameter with trust[seg] != 0 takes g = (g + wd * p) * trust[seg], and EVERY member
+ * of a lars_group group steps with weight decay 0.  Same arithmetic per element as the two entry points above; 16-byte loads /
+ * stores where a block's first element is 16-byte aligned in every buffer.  Skipped when ctl[2] != 0. */
+int sf_flat_sgd_tab(float* param, const float* grad, float* mom, const void* segs, const int32_t* blk_seg, const int32_t* blk_off,
+                    int32_t nblocks, const float* ctl, const float* hyper, const float* trust, float clip_val, float momentum,
+                    float dampening, int nesterov, sf_stream_t stream);
+int sf_flat_adamw_tab(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const void* segs, const int32_t* blk_seg,
+                      const int32_t* blk_off, int32_t nblocks, const float* ctl, const float* hyper, const float* trust,
+                      float clip_val, float beta1, float beta2, float eps, sf_stream_t stream);
+/* LARS trust ratios (optimizer.py:321-359), after sf_step_control (reads ctl[4]) and before the table-driven update.  Two
+ * launches, no atomics: per-block sum p^2 / sum g_eff^2 (g_eff = clip_val(grad * ctl[4]), the gradient the update sees) in
+ * double into part [nblocks][2], then one workgroup per segment sums its rows seg_row[s] .. seg_row[s + 1] - 1 ([nseg + 1] int32)
+ * in a fixed order and writes trust[s] = trust_coef * |p| / (|g| + |p| * wd + eps); 0 = "leave the gradient alone" for a segment
+ * whose flags word (the segment table's `pad`) has bit 0 clear (1-D parameter), whose group has lars_group 0, or whose |p| or
+ * |g| is zero.  Both launches return at once when ctl[2] != 0 (trust keeps its previous content). */
+int sf_flat_lars_trust(const float* param, const float* grad, const void* segs, const int32_t* blk_seg, const int32_t* blk_off,
+                       int32_t nblocks, const int32_t* seg_row, int32_t nseg, const float* ctl, const float* hyper, double* part,
+                       float* trust, float clip_val, float trust_coef, float eps, sf_stream_t stream);
 
 #ifdef __cplusplus
 }

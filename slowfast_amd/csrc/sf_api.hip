@@ -2727,3 +2727,51 @@ extern "C" int sf_flat_adamw(float* param, const float* grad, float* exp_avg, fl
     hipLaunchKernelGGL(sf_flat_adamw_kernel, dim3(nblocks), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("flat_adamw");
 }
+
+// Table-driven update (ABI 24): per-group hyper-parameters in device memory, any number of groups, optional LARS
+// (slowfast/models/optimizer.py:146-237 and :262-359).
+static int fill_flat_tab(FlatTabParams& p, float* param, const float* grad, float* m1, float* m2, const void* segs,
+                         const int32_t* blk_seg, const int32_t* blk_off, int32_t nblocks, const float* ctl, const float* hyper,
+                         const float* trust, float clip_val) {
+    REQUIRE(param && grad && segs && blk_seg && blk_off && ctl && hyper && nblocks > 0, "flat table update: bad arguments");
+    REQUIRE((uintptr_t)hyper % 16 == 0, "flat table update: hyper must be 16-byte aligned");
+    memset(&p, 0, sizeof(p));
+    p.param = param; p.grad = grad; p.m1 = m1; p.m2 = m2; p.segs = (const FlatSeg*)segs; p.blk_seg = blk_seg; p.blk_off = blk_off;
+    p.ctl = ctl; p.hyper = hyper; p.trust = trust; p.clip_val = clip_val;
+    return 0;
+}
+extern "C" int sf_flat_sgd_tab(float* param, const float* grad, float* mom, const void* segs, const int32_t* blk_seg,
+                               const int32_t* blk_off, int32_t nblocks, const float* ctl, const float* hyper, const float* trust,
+                               float clip_val, float momentum, float dampening, int nesterov, sf_stream_t stream) {
+    FlatTabParams p;
+    if (fill_flat_tab(p, param, grad, mom, nullptr, segs, blk_seg, blk_off, nblocks, ctl, hyper, trust, clip_val)) return -1;
+    REQUIRE(momentum == 0.f || mom, "sf_flat_sgd_tab: momentum needs a buffer");
+    p.momentum = momentum; p.dampening = dampening; p.nesterov = nesterov;
+    hipLaunchKernelGGL(sf_flat_sgd_tab_kernel, dim3(nblocks), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("flat_sgd_tab");
+}
+extern "C" int sf_flat_adamw_tab(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const void* segs,
+                                 const int32_t* blk_seg, const int32_t* blk_off, int32_t nblocks, const float* ctl,
+                                 const float* hyper, const float* trust, float clip_val, float beta1, float beta2, float eps,
+                                 sf_stream_t stream) {
+    FlatTabParams p;
+    if (fill_flat_tab(p, param, grad, exp_avg, exp_avg_sq, segs, blk_seg, blk_off, nblocks, ctl, hyper, trust, clip_val)) return -1;
+    REQUIRE(exp_avg && exp_avg_sq, "sf_flat_adamw_tab: moment buffers");
+    p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
+    hipLaunchKernelGGL(sf_flat_adamw_tab_kernel, dim3(nblocks), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("flat_adamw_tab");
+}
+extern "C" int sf_flat_lars_trust(const float* param, const float* grad, const void* segs, const int32_t* blk_seg,
+                                  const int32_t* blk_off, int32_t nblocks, const int32_t* seg_row, int32_t nseg, const float* ctl,
+                                  const float* hyper, double* part, float* trust, float clip_val, float trust_coef, float eps,
+                                  sf_stream_t stream) {
+    REQUIRE(param && grad && segs && blk_seg && blk_off && seg_row && ctl && hyper && part && trust, "sf_flat_lars_trust: null pointer");
+    REQUIRE(nblocks > 0 && nseg > 0 && nseg <= nblocks && trust_coef > 0.f && eps >= 0.f, "sf_flat_lars_trust: bad arguments");
+    FlatLarsParams p;
+    p.param = param; p.grad = grad; p.segs = (const FlatSeg*)segs; p.blk_seg = blk_seg; p.blk_off = blk_off; p.seg_row = seg_row;
+    p.ctl = ctl; p.hyper = hyper; p.part = part; p.trust = trust; p.clip_val = clip_val; p.trust_coef = trust_coef; p.eps = eps;
+    hipLaunchKernelGGL(sf_flat_lars_norms_kernel, dim3(nblocks), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    if (check_launch("flat_lars_norms")) return -1;
+    hipLaunchKernelGGL(sf_flat_lars_trust_kernel, dim3(nseg), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("flat_lars_trust");
+}

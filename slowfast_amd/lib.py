@@ -11,7 +11,7 @@ import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 23
+ABI_VERSION = 24
 # 16-bit storage type of activations / packed weights / MFMA operands, fixed per PROCESS: SF_ACT_DTYPE=fp16 (default) loads
 # libsfamd.so, =bf16 loads libsfamd_bf16.so -- the same sources compiled with -DSF_ACT_BF16 (bfloat16 storage,
 # v_mfma_f32_16x16x32_bf16); both are what torch.cuda.amp.autocast admits on the reference side (tools/train_net.py:101-118).
@@ -107,6 +107,9 @@ _SIGNATURES = {
     "sf_step_control": (c_int, [_F, c_int32, _F, c_float, c_float, c_int, c_float, c_float, c_int32, _P]),
     "sf_flat_sgd": (c_int, [_F, _F, _F, _P, _P, _P, c_int32, _F, _P, _P, c_int32, c_float, c_float, c_float, c_int, _P]),
     "sf_flat_adamw": (c_int, [_F, _F, _F, _F, _P, _P, _P, c_int32, _F, _P, _P, c_int32, c_float, c_float, c_float, c_float, _P]),
+    "sf_flat_sgd_tab": (c_int, [_F, _F, _F, _P, _P, _P, c_int32, _F, _F, _F, c_float, c_float, c_float, c_int, _P]),
+    "sf_flat_adamw_tab": (c_int, [_F, _F, _F, _F, _P, _P, _P, c_int32, _F, _F, _F, c_float, c_float, c_float, c_float, _P]),
+    "sf_flat_lars_trust": (c_int, [_F, _F, _P, _P, _P, c_int32, _P, c_int32, _F, _F, _P, _F, c_float, c_float, c_float, _P]),
     "sf_bn_bwd_reduce": (c_int, [c_int64, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, _F, _F, c_int, _F, _P]),
     "sf_bn_bwd_finalize": (c_int, [_F, c_int32, c_int32, c_int32, c_float, _F, _F, _F, c_float, _F, _F, c_int, _F, _P]),
     "sf_bn_bwd_apply": (c_int, [c_int64, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, _F, _F, c_int, _F, _P,

@@ -9,8 +9,14 @@ an 8-word control block in device memory.
 
 Parameters are re-pointed to views of ONE flat fp32 buffer laid out like GradReducer.flat (gradients) and the optimizer
 state, so the update is a single pass over contiguous memory.  ``param_groups`` mirrors torch.optim (lists of dicts with
-"lr" / "weight_decay"), so the reference's ``optim.set_lr(optimizer, lr)`` (slowfast/models/optimizer.py:143-152) keeps
-working on it.
+"lr" / "weight_decay" / "layer_decay" / "apply_LARS"), so the reference's ``optim.set_lr(optimizer, lr)``
+(slowfast/models/optimizer.py:251-259, ``set_lr`` below) keeps working on it.
+
+Two update paths (FlatOptimizer.table_path).  Up to 8 groups without LARS: sf_flat_sgd / sf_flat_adamw, lr / weight decay as
+kernel arguments.  More groups (SOLVER.LAYER_DECAY < 1 makes 2 * (MVIT.DEPTH + 2) of them) or LARS: sf_flat_sgd_tab /
+sf_flat_adamw_tab read ``hyper`` -- a DEVICE table [ngroups][4] = lr, weight decay, lars_group, reserved -- so a new learning
+rate reaches a captured launch on its next replay; LARS (optimizer.py:262-359) adds sf_flat_lars_trust (two launches: per-block
+norms, per-parameter trust ratio) between the control launch and the update.
 """
 from ctypes import c_float
 
@@ -22,6 +28,8 @@ from .lib import get_lib
 
 _SEG_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("group", "<i4"), ("pad", "<i4")])
 _BLOCK = 1024       # elements per workgroup of the update kernels (SF_OPT_BLOCK_ELEMS)
+_MAX_ARG_GROUPS = 8 # SF_OPT_MAX_GROUPS: what sf_flat_sgd / sf_flat_adamw carry by value
+_SEG_LARS = 1       # segment flags word (the table's `pad`), bit 0: LARS adapts this parameter (it is not 1-D)
 CTL_SCALE, CTL_TRACKER, CTL_FOUND_INF, CTL_GRAD_NORM, CTL_MULT, CTL_STEPS, CTL_SKIPPED = range(7)
 
 
@@ -32,11 +40,18 @@ def _stream(t):
 class FlatOptimizer:
     def __init__(self, param_groups, reducer, method="sgd", momentum=0.0, dampening=0.0, nesterov=False, betas=(0.9, 0.999),
                  eps=1e-8, loss_scale=1.0, dynamic_loss_scale=False, growth_factor=2.0, backoff_factor=0.5,
-                 growth_interval=2000, clip_grad_l2norm=None, clip_grad_val=None):
+                 growth_interval=2000, clip_grad_l2norm=None, clip_grad_val=None, lars=False, trust_coefficient=0.001,
+                 lars_eps=1e-8):
         assert method in ("sgd", "adamw")
         groups = [dict(g) for g in param_groups]
-        assert 1 <= len(groups) <= 8, "1..8 parameter groups"
+        assert len(groups) >= 1, "at least one parameter group"
+        for g in groups:
+            g.setdefault("layer_decay", 1.0)                # optimizer.py:58-77, :202-212
+            g.setdefault("apply_LARS", bool(lars))          # LARS.step(): a group without the key is adapted
         self.param_groups = groups
+        self.lars, self.trust_coefficient, self.lars_eps = bool(lars), float(trust_coefficient), float(lars_eps)
+        assert not self.lars or (self.trust_coefficient > 0.0 and self.lars_eps >= 0.0)
+        self.table_path = self.lars or len(groups) > _MAX_ARG_GROUPS
         self.method, self.momentum, self.dampening, self.nesterov = method, float(momentum), float(dampening), bool(nesterov)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.dynamic = bool(dynamic_loss_scale)
@@ -53,7 +68,8 @@ class FlatOptimizer:
                 group_of[p] = gi
         # parameters become views of one flat buffer with the gradient buffer's layout
         self.flat_param = torch.empty_like(flat_g)
-        segs, blk_seg, blk_off = [], [], []
+        segs, blk_seg, blk_off, seg_row = [], [], [], []
+        self._seg_of = {}
         off = 0
         for p in reducer.params:
             n = p.numel()
@@ -61,8 +77,9 @@ class FlatOptimizer:
             view = self.flat_param[off:off + n].view_as(p)
             view.copy_(p.data)
             p.data = view
-            si = len(segs)
-            segs.append((off, off + n, group_of[p], 0))
+            si = self._seg_of[id(p)] = len(segs)
+            segs.append((off, off + n, group_of[p], _SEG_LARS if p.dim() != 1 else 0))    # LARS(ignore_1d_param=True)
+            seg_row.append(len(blk_seg))
             for b in range(0, n, _BLOCK):
                 blk_seg.append(si)
                 blk_off.append(b)
@@ -87,6 +104,16 @@ class FlatOptimizer:
             r += nb
         self._part = torch.empty((max(r, lib.call("sf_flat_blocks", flat_g.numel())), 2), dtype=torch.float32, device=dev)
         self._rows_bucketed = r
+        self.hyper = self._hyper_host = None
+        if self.table_path:
+            self.hyper = torch.zeros((len(groups), 4), dtype=torch.float32, device=dev)
+            self._hyper_host = None                          # what `hyper` holds (numpy), None: nothing uploaded yet
+            self._stage, self._stage_i = [None, None], 0     # pinned staging buffers + the event of their last upload
+            self.sync_hyper()
+        if self.lars:
+            self.seg_row = torch.tensor(seg_row + [len(blk_seg)], dtype=torch.int32, device=dev)
+            self.trust = torch.zeros(len(segs), dtype=torch.float32, device=dev)
+            self._lars_part = torch.empty((self.nblocks, 2), dtype=torch.float64, device=dev)
 
     # -- what the training loop touches ---------------------------------------------------------------------------
     @property
@@ -103,6 +130,42 @@ class FlatOptimizer:
     @property
     def found_inf(self):
         return self.ctl[CTL_FOUND_INF]
+
+    def _hyper_rows(self):
+        return np.array([[float(g["lr"]), float(g.get("weight_decay", 0.0)), float(self.lars and bool(g["apply_LARS"])), 0.0]
+                         for g in self.param_groups], dtype=np.float32)
+
+    def sync_hyper(self):
+        """Upload lr / weight decay / LARS membership of ``param_groups`` into the device table the table-driven kernels read,
+        if a value changed since the last upload.  step() calls it; call it yourself between replays of a graph that captured
+        step() (never inside a capture: the upload is a copy, not a kernel).  The copy is asynchronous on the current stream
+        from one of two pinned staging buffers, so a per-iteration learning-rate schedule costs no host synchronisation."""
+        if not self.table_path:
+            return False
+        rows = self._hyper_rows()
+        if self._hyper_host is not None and np.array_equal(rows, self._hyper_host):
+            return False
+        if self.hyper.is_cuda:
+            assert not torch.cuda.is_current_stream_capturing(), "sync_hyper() inside a graph capture"
+            i = self._stage_i = self._stage_i ^ 1
+            if self._stage[i] is None:
+                self._stage[i] = [torch.empty(rows.shape, dtype=torch.float32).pin_memory(), None]
+            buf, ev = self._stage[i]
+            if ev is not None:
+                ev.synchronize()                             # two uploads ago: long done
+            buf.copy_(torch.from_numpy(rows))
+            self.hyper.copy_(buf, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.hyper.device))
+            self._stage[i][1] = ev
+        else:
+            self.hyper.copy_(torch.from_numpy(rows))
+        self._hyper_host = rows
+        return True
+
+    def trust_ratio(self, p):
+        """LARS trust ratio parameter ``p`` took in the last clean step (0-d device tensor; 0: its gradient was not scaled)."""
+        return self.trust[self._seg_of[id(p)]]
 
     def _sumsq_bucket(self, bi):
         """Bucket bi's share of the norm / overflow pass (its own rows of the partial table)."""
@@ -131,6 +194,10 @@ class FlatOptimizer:
             lib.call("sf_flat_sumsq", g.data_ptr(), g.numel(), self._part.data_ptr(), s, work=dict(bytes=4.0 * g.numel()))
         lib.call("sf_step_control", self._part.data_ptr(), nrows, self.ctl.data_ptr(), float(self.reducer.world),
                  self.clip_norm, int(self.dynamic), self.growth, self.backoff, self.growth_interval, s)
+        if self.table_path:
+            self._step_table(lib, g, s)
+            engine.PARAM_EPOCH += 1
+            return
         ng = len(self.param_groups)
         lr = (c_float * ng)(*[float(gp["lr"]) for gp in self.param_groups])
         wd = (c_float * ng)(*[float(gp.get("weight_decay", 0.0)) for gp in self.param_groups])
@@ -145,6 +212,27 @@ class FlatOptimizer:
                      lr, wd, ng, self.clip_val, self.betas[0], self.betas[1], self.eps, s, work=dict(bytes=4.0 * g.numel() * 7))
         engine.PARAM_EPOCH += 1         # the kernels wrote the parameters without bumping tensor._version: packed-weight
                                         # caches of the eager path must not be reused (a captured graph re-packs anyway)
+
+    def _step_table(self, lib, g, s):
+        """[LARS trust ratios +] table-driven update: hyper-parameters from device memory."""
+        if not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
+            self.sync_hyper()
+        n = g.numel()
+        tables = (self.segs.data_ptr(), self.blk_seg.data_ptr(), self.blk_off.data_ptr(), self.nblocks)
+        trust = None
+        if self.lars:
+            lib.call("sf_flat_lars_trust", self.flat_param.data_ptr(), g.data_ptr(), *tables, self.seg_row.data_ptr(),
+                     self.trust.numel(), self.ctl.data_ptr(), self.hyper.data_ptr(), self._lars_part.data_ptr(),
+                     self.trust.data_ptr(), self.clip_val, self.trust_coefficient, self.lars_eps, s, work=dict(bytes=8.0 * n))
+            trust = self.trust.data_ptr()
+        if self.method == "sgd":
+            lib.call("sf_flat_sgd_tab", self.flat_param.data_ptr(), g.data_ptr(), self.m1.data_ptr() if self.m1 is not None else None,
+                     *tables, self.ctl.data_ptr(), self.hyper.data_ptr(), trust, self.clip_val, self.momentum, self.dampening,
+                     int(self.nesterov), s, work=dict(bytes=4.0 * n * (3 + 2 * int(self.m1 is not None))))
+        else:
+            lib.call("sf_flat_adamw_tab", self.flat_param.data_ptr(), g.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr(),
+                     *tables, self.ctl.data_ptr(), self.hyper.data_ptr(), trust, self.clip_val, self.betas[0], self.betas[1],
+                     self.eps, s, work=dict(bytes=4.0 * n * 7))
 
     def zero_grad(self, set_to_none=False):
         self.reducer.zero_grad()
@@ -165,23 +253,8 @@ class FlatOptimizer:
             g.update(s)
 
 
-def construct_optimizer(model, cfg, reducer, loss_scale=1.0, dynamic_loss_scale=None):
-    """FlatOptimizer configured as slowfast/models/optimizer.py:9-140 configures torch's (the ``LAYER_DECAY == 1.0`` branch,
-    :26-92): BatchNorm parameters get BN.WEIGHT_DECAY; parameters whose dotted name contains an entry of
-    ``model.no_weight_decay()`` (MViT: pos_embed* / rel_pos_* / cls_token under MVIT.ZERO_DECAY_POS_CLS) get no decay; so do
-    1-D parameters and every ``*.bias`` when SOLVER.ZERO_WD_1D_PARAM; the rest SOLVER.WEIGHT_DECAY.
-    SOLVER.OPTIMIZING_METHOD "sgd" (momentum / dampening / nesterov) or "adamw" / "mt_adamw" (SOLVER.BETAS, eps 1e-8);
-    clipping from SOLVER.CLIP_GRAD_L2NORM / CLIP_GRAD_VAL; the dynamic loss scale defaults to TRAIN.MIXED_PRECISION
-    (GradScaler's constants).  Options the fused kernels do not implement raise instead of silently changing the update rule:
-    SOLVER.LAYER_DECAY != 1 (per-layer lr scale, optimizer.py:155-220), SOLVER.LARS_ON, "adam" (L2-coupled decay)."""
-    layer_decay = float(cfg.SOLVER.get("LAYER_DECAY", 1.0))
-    if not 0.0 < layer_decay <= 1.0:
-        raise ValueError("Layer decay should be in (0, 1], but is {}".format(layer_decay))
-    if layer_decay != 1.0:
-        raise NotImplementedError("SOLVER.LAYER_DECAY < 1 (per-layer learning-rate scale) is not built into FlatOptimizer")
-    if cfg.SOLVER.get("LARS_ON", False):
-        raise NotImplementedError("SOLVER.LARS_ON is not built into FlatOptimizer")
-    inner = model.module if hasattr(model, "module") and isinstance(model.module, torch.nn.Module) else model
+def _flat_groups(inner, cfg, lr, lars):
+    """The LAYER_DECAY == 1 grouping (slowfast/models/optimizer.py:27-78)."""
     skip = inner.no_weight_decay() if hasattr(inner, "no_weight_decay") else ()
     bn, rest, zero = [], [], []
     seen = set()
@@ -200,13 +273,83 @@ def construct_optimizer(model, cfg, reducer, loss_scale=1.0, dynamic_loss_scale=
                 zero.append(p)
             else:
                 rest.append(p)
+    return [g for g in ({"params": bn, "weight_decay": cfg.BN.WEIGHT_DECAY, "lr": lr, "layer_decay": 1.0, "apply_LARS": False},
+                        {"params": rest, "weight_decay": cfg.SOLVER.WEIGHT_DECAY, "lr": lr, "layer_decay": 1.0, "apply_LARS": lars},
+                        {"params": zero, "weight_decay": 0.0, "lr": lr, "layer_decay": 1.0, "apply_LARS": lars}) if g["params"]]
+
+
+def set_lr(optimizer, new_lr):
+    """slowfast/models/optimizer.py:251-259: every group's lr becomes ``new_lr * group["layer_decay"]`` (the per-layer scale of
+    SOLVER.LAYER_DECAY is applied here and nowhere else).  On the table path the new values reach the device with the next
+    step() / sync_hyper()."""
+    for param_group in optimizer.param_groups:
+        param_group["lr"] = new_lr * param_group["layer_decay"]
+
+
+def _layer_decay_groups(inner, cfg):
+    """get_param_groups (slowfast/models/optimizer.py:146-237): one group per (layer id, decayed or not), in order of first
+    appearance; layer ids cls_token / mask_token / pos_embed* / patch_embed* -> 0, blocks.N.* -> N + 1, the rest
+    MVIT.DEPTH + 1; ``layer_decay = SOLVER.LAYER_DECAY ** (MVIT.DEPTH + 1 - layer id)``.  ``name in skip`` is an exact match
+    here (the LAYER_DECAY == 1 branch tests substrings)."""
+    for m in inner.modules():
+        assert not isinstance(m, torch.nn.modules.batchnorm._NormBase), "BN is not supported with layer decay"
+    depth, decay = int(cfg.MVIT.DEPTH), float(cfg.SOLVER.LAYER_DECAY)
+    skip = inner.no_weight_decay() if hasattr(inner, "no_weight_decay") else {}
+
+    def layer_id(name):
+        if name in ("cls_token", "mask_token") or name.startswith("pos_embed") or name.startswith("patch_embed"):
+            return 0
+        if name.startswith("blocks"):
+            return int(name.split(".")[1]) + 1
+        return depth + 1
+
+    groups, counted = {}, 0
+    for name, p in inner.named_parameters():
+        counted += 1
+        if not p.requires_grad:
+            continue
+        name = name[len("module."):] if name.startswith("module.") else name
+        zero = name in skip or ((p.dim() == 1 or name.endswith(".bias")) and cfg.SOLVER.ZERO_WD_1D_PARAM)
+        lid = layer_id(name)
+        key = "layer_%d_%s" % (lid, "zero" if zero else "non_bn")
+        if key not in groups:
+            groups[key] = {"params": [], "weight_decay": 0.0 if zero else cfg.SOLVER.WEIGHT_DECAY,
+                           "layer_decay": decay ** (depth + 1 - lid)}
+        groups[key]["params"].append(p)
+    assert counted == len(list(inner.parameters())), "parameter size does not match"
+    return list(groups.values())
+
+
+def construct_optimizer(model, cfg, reducer, loss_scale=1.0, dynamic_loss_scale=None):
+    """FlatOptimizer configured as slowfast/models/optimizer.py:9-143 configures torch's.
+
+    ``SOLVER.LAYER_DECAY == 1`` (:26-92): BatchNorm parameters get BN.WEIGHT_DECAY; parameters whose dotted name contains an
+    entry of ``model.no_weight_decay()`` (MViT: pos_embed* / rel_pos_* / cls_token under MVIT.ZERO_DECAY_POS_CLS) get no decay;
+    so do 1-D parameters and every ``*.bias`` when SOLVER.ZERO_WD_1D_PARAM; the rest SOLVER.WEIGHT_DECAY.  Every group carries
+    ``layer_decay 1.0`` and ``apply_LARS`` (False for BatchNorm, SOLVER.LARS_ON for the other two).
+    ``0 < SOLVER.LAYER_DECAY < 1`` (:146-237, get_param_groups): one group per layer id and decay class, each with its
+    ``layer_decay``; the lr of every group starts at BASE_LR and the per-layer scale is applied by ``set_lr`` -- as in the
+    reference.  These are more than 8 groups for any real depth: FlatOptimizer takes its table-driven path.
+    SOLVER.LARS_ON (:141-142, :262-359): ``FlatOptimizer(lars=True, trust_coefficient=0.001)``, clip=False semantics.
+    SOLVER.OPTIMIZING_METHOD "sgd" (momentum / dampening / nesterov) or "adamw" / "mt_adamw" (SOLVER.BETAS, eps 1e-8);
+    clipping from SOLVER.CLIP_GRAD_L2NORM / CLIP_GRAD_VAL; the dynamic loss scale defaults to TRAIN.MIXED_PRECISION
+    (GradScaler's constants).  "adam" (L2-coupled decay) is not built into the fused kernels and raises instead of silently
+    changing the update rule."""
+    layer_decay = float(cfg.SOLVER.get("LAYER_DECAY", 1.0))
+    if not 0.0 < layer_decay <= 1.0:
+        raise ValueError("Layer decay should be in (0, 1], but is {}".format(layer_decay))
+    lars = bool(cfg.SOLVER.get("LARS_ON", False))
+    inner = model.module if hasattr(model, "module") and isinstance(model.module, torch.nn.Module) else model
     lr = cfg.SOLVER.BASE_LR
-    groups = [g for g in ({"params": bn, "weight_decay": cfg.BN.WEIGHT_DECAY, "lr": lr},
-                          {"params": rest, "weight_decay": cfg.SOLVER.WEIGHT_DECAY, "lr": lr},
-                          {"params": zero, "weight_decay": 0.0, "lr": lr}) if g["params"]]
+    if layer_decay != 1.0:
+        groups = _layer_decay_groups(inner, cfg)
+        for g in groups:
+            g["lr"] = lr
+    else:
+        groups = _flat_groups(inner, cfg, lr, lars)
     dyn = bool(cfg.TRAIN.MIXED_PRECISION) if dynamic_loss_scale is None else dynamic_loss_scale
     kw = dict(loss_scale=loss_scale, dynamic_loss_scale=dyn, clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM,
-              clip_grad_val=cfg.SOLVER.CLIP_GRAD_VAL)
+              clip_grad_val=cfg.SOLVER.CLIP_GRAD_VAL, lars=lars, trust_coefficient=0.001)
     method = cfg.SOLVER.OPTIMIZING_METHOD
     if method in ("adamw", "mt_adamw"):
         betas = tuple(cfg.SOLVER.get("BETAS", (0.9, 0.999)))
