@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 24
+#define SF_ABI_VERSION 25
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -388,6 +388,31 @@ int sf_gemm_act_colsum(int64_t M, int32_t N, int32_t K, const void* A, int32_t l
 int sf_pack_clip_u8(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index, int32_t Tout,
                     float mean0, float mean1, float mean2, float std0, float std1, float std2, int32_t reverse, void* out,
                     sf_stream_t stream);
+/* MixUp / CutMix of the batch (ABI 25) -- replaces mixup_fn(inputs[0], labels) of the training loop (tools/train_net.py:109-111,
+ * slowfast/datasets/mixup.py).  Sample i is mixed with sample B-1-i (x.flip(0)).  lam and one_minus_lam are the host's doubles
+ * lam and 1.0 - lam, EACH rounded to float (1.0f - (float)lam is a different number); every blend is
+ * fl(fl(a * lam) + fl(b * one_minus_lam)) with no contraction, bit for bit x.mul_(lam).add_(x.flip(0).mul_(1 - lam)).
+ * Kernel launches only; scalars travel as kernel arguments (the calls run eagerly, outside a captured graph).
+ *
+ * sf_mix_clip_f32: dense fp32 clip [B][C][T][H][W].  dst == src mixes in place, any other dst must not overlap src.
+ *   mode 0 (mixup):  dst[i] = src[i] * lam + src[B-1-i] * one_minus_lam; the box is ignored.  The middle sample of an odd batch
+ *                    is mixed with itself (not the identity).
+ *   mode 1 (cutmix): rows yl..yh-1, columns xl..xh-1 of every (c, t) plane of dst[i] come from src[B-1-i]; everything else is
+ *                    src[i] (in place: untouched; an empty box launches nothing).  lam / one_minus_lam are ignored. */
+int sf_mix_clip_f32(const float* src, float* dst, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int32_t mode,
+                    float lam, float one_minus_lam, int32_t yl, int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream);
+/* sf_pack_clip_u8 with the batch mixed in fp32 BETWEEN the normalisation and the rounding to the 16-bit storage type (mixing
+ * the packed buffer afterwards would round twice): frame n and -- for mixup, or inside the cutmix box -- frame N-1-n are
+ * normalised as sf_pack_clip_u8 does, mixed as sf_mix_clip_f32 does, rounded once.  Arguments of sf_pack_clip_u8 + the mix. */
+int sf_pack_clip_u8_mix(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index, int32_t Tout,
+                        float mean0, float mean1, float mean2, float std0, float std1, float std2, int32_t reverse, void* out,
+                        int32_t mode, float lam, float one_minus_lam, int32_t yl, int32_t yh, int32_t xl, int32_t xh,
+                        sf_stream_t stream);
+/* mixup_target() (datasets/mixup.py:40-64) in one launch: out[i][k] = v(i, k) * lam + v(B-1-i, k) * one_minus_lam, where
+ * v(i, k) = on_value when k == labels[i] and off_value otherwise (floats rounded from the host's doubles 1 - s + s / K and
+ * s / K, s = label smoothing).  labels int64 [B] on the device, out fp32 [B][K] (may be a step's static label buffer). */
+int sf_mix_targets(const int64_t* labels, int32_t B, int32_t K, float on_value, float off_value, float lam, float one_minus_lam,
+                   float* out, sf_stream_t stream);
 /* Stochastic depth -- replaces drop_path() (slowfast/models/common.py:46-59) at the two residual additions of
  * MultiScaleBlock (attention.py:500-510): y[m] = (resid ? resid[m] : 0) + scale[m / rows_per_sample] * x[m], with
  * scale[b] = floor(keep_prob + u_b) / keep_prob sampled by the caller.  Rows are fp16 [M][C], C % 8 == 0. */

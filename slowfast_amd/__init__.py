@@ -11,3 +11,5 @@ from . import video_models  # noqa: F401,E402  (registers SlowFast / ResNet in M
 from . import mvit  # noqa: F401,E402  (registers MViT)
 from . import x3d  # noqa: F401,E402  (registers X3D, the x3d_stem and x3d_transform factories)
 from .data import pack_pathways_u8  # noqa: F401,E402  (uint8 frames -> stem operand layout)
+from .mixup import MixUp, construct_mixup  # noqa: F401,E402  (MixUp / CutMix of the batch on the device)
+from .losses import get_loss_func  # noqa: F401,E402

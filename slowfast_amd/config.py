@@ -117,7 +117,9 @@ _DEFAULTS = {
     # slowfast/config/defaults.py:333-358
     "X3D": {"WIDTH_FACTOR": 1.0, "DEPTH_FACTOR": 1.0, "BOTTLENECK_FACTOR": 1.0, "DIM_C5": 2048, "DIM_C1": 12,
             "SCALE_RES2": False, "BN_LIN5": False, "CHANNELWISE_3x3x3": True},
-    "MIXUP": {"ENABLE": False},
+    # slowfast/config/defaults.py:239-257
+    "MIXUP": {"ENABLE": False, "ALPHA": 0.8, "CUTMIX_ALPHA": 1.0, "PROB": 1.0, "SWITCH_PROB": 0.5,
+              "LABEL_SMOOTH_VALUE": 0.1},
     "NUM_GPUS": 1, "NUM_SHARDS": 1, "SHARD_ID": 0, "RNG_SEED": 1, "LOG_MODEL_INFO": True, "DIST_BACKEND": "nccl",
     "OUTPUT_DIR": ".",
 }

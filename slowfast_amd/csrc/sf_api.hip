@@ -15,6 +15,7 @@
 #include "sf_attn.h"
 #include "sf_roi.h"
 #include "sf_optim.h"
+#include "sf_mixup.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2472,6 +2473,99 @@ extern "C" int sf_pack_clip_u8(const void* frames, int32_t N, int32_t Tin, int32
     p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)Tout);
     hipLaunchKernelGGL(sf_pack_clip_u8_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("pack_clip_u8");
+}
+
+// ================================================================================================
+// MixUp / CutMix of the batch (sf_mixup.h; replaces mixup_fn(inputs[0], labels), tools/train_net.py:109-111).  Kernel
+// launches only, scalars by value: they run eagerly between two replays and write the step's static buffers.
+static const int kMixBlocks = 2048;         // 256 CUs x 8 resident blocks; the rest of the clip is grid-strided
+static int mix_grid_x(int64_t items, int rows) {
+    int64_t b = (items + SF_THREADS - 1) / SF_THREADS;
+    const int64_t cap = kMixBlocks / rows > 0 ? kMixBlocks / rows : 1;
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+static int check_mix_box(const char* who, int32_t mode, int32_t H, int32_t W, int32_t yl, int32_t yh, int32_t xl, int32_t xh) {
+    REQUIRE(mode == 0 || mode == 1, "%s: mode must be 0 (mixup) or 1 (cutmix)", who);
+    REQUIRE(mode == 0 || (0 <= yl && yl <= yh && yh <= H && 0 <= xl && xl <= xh && xh <= W),
+            "%s: box rows [%d, %d) columns [%d, %d) outside the %d x %d plane", who, yl, yh, xl, xh, H, W);
+    return 0;
+}
+extern "C" int sf_mix_clip_f32(const float* src, float* dst, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W,
+                               int32_t mode, float lam, float one_minus_lam, int32_t yl, int32_t yh, int32_t xl, int32_t xh,
+                               sf_stream_t stream) {
+    REQUIRE(src && dst, "sf_mix_clip_f32: null pointer");
+    REQUIRE(B > 0 && B < 65536 && C > 0 && T > 0 && H > 0 && W > 0, "sf_mix_clip_f32: bad shape");
+    if (check_mix_box("sf_mix_clip_f32", mode, H, W, yl, yh, xl, xh)) return -1;
+    MixClipParams p;
+    memset(&p, 0, sizeof(p));
+    p.S = (int64_t)C * T * H * W;
+    REQUIRE(p.S < (1ll << 31), "sf_mix_clip_f32: more than 2^31 elements per sample");
+    REQUIRE((uintptr_t)src % 4 == 0 && (uintptr_t)dst % 4 == 0, "sf_mix_clip_f32: buffers must be 4-byte aligned");
+    const bool inplace = (const float*)dst == src;
+    REQUIRE(inplace || dst + (int64_t)B * p.S <= src || src + (int64_t)B * p.S <= dst,
+            "sf_mix_clip_f32: dst must be src (in place) or must not overlap it");
+    p.src = src; p.dst = dst; p.B = B; p.H = H; p.W = W; p.lam = lam; p.oml = one_minus_lam;
+    p.yl = yl; p.yh = yh; p.xl = xl; p.xh = xh;
+    const bool aligned = (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 && p.S % 4 == 0;
+    const int64_t planes = (int64_t)C * T;
+    if (mode == 0) {
+        const int pairs = (B + 1) / 2;
+        const int64_t n = aligned ? p.S / 4 : p.S;
+        dim3 grid(mix_grid_x(n, pairs), pairs);
+        if (aligned) hipLaunchKernelGGL(sf_mixup_clip_kernel<4>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(sf_mixup_clip_kernel<1>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+        return check_launch("mix_clip_f32 (mixup)");
+    }
+    p.vec_ok = aligned && W % 4 == 0;
+    if (inplace) {
+        const int pairs = B / 2;                            // the middle sample of an odd batch is left as it is
+        if (yl == yh || xl == xh || pairs == 0) return 0;   // empty box: nothing to swap
+        p.g0 = xl / 4;
+        const int ngroups = (xh - 1) / 4 - p.g0 + 1;
+        p.fdG = make_fastdiv((uint32_t)ngroups); p.fdR = make_fastdiv((uint32_t)(yh - yl));
+        p.items = planes * (yh - yl) * ngroups;
+        hipLaunchKernelGGL(sf_cutmix_swap_kernel, dim3(mix_grid_x(p.items, pairs), pairs), dim3(SF_THREADS), 0,
+                           (hipStream_t)stream, p);
+        return check_launch("mix_clip_f32 (cutmix)");
+    }
+    const int ngroups = (W + 3) / 4;
+    p.fdG = make_fastdiv((uint32_t)ngroups); p.fdR = make_fastdiv((uint32_t)H);
+    p.items = planes * H * ngroups;
+    hipLaunchKernelGGL(sf_cutmix_copy_kernel, dim3(mix_grid_x(p.items, B), B), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("mix_clip_f32 (cutmix copy)");
+}
+extern "C" int sf_pack_clip_u8_mix(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
+                                   int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                                   int32_t reverse, void* out, int32_t mode, float lam, float one_minus_lam, int32_t yl,
+                                   int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream) {
+    REQUIRE(frames && out, "sf_pack_clip_u8_mix: null pointer");
+    REQUIRE(N > 0 && Tin > 0 && Tout > 0 && H > 0 && W > 0 && W % 2 == 0, "sf_pack_clip_u8_mix: bad shape (W must be even)");
+    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_pack_clip_u8_mix: zero std");
+    if (check_mix_box("sf_pack_clip_u8_mix", mode, H, W, yl, yh, xl, xh)) return -1;
+    PackClipMixParams m;
+    memset(&m, 0, sizeof(m));
+    PackClipParams& p = m.k;
+    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = Tin; p.Tout = Tout; p.HW = (int64_t)H * W;
+    p.t_index = t_index; p.reverse = reverse; p.out = (f16*)out;
+    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
+    p.total = (int64_t)N * Tout * p.HW;
+    REQUIRE(p.total < (1ll << 31) && (int64_t)N * Tin * p.HW < (1ll << 40), "sf_pack_clip_u8_mix: too many pixels");
+    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)Tout);
+    m.W = W; m.mode = mode; m.lam = lam; m.oml = one_minus_lam; m.yl = yl; m.yh = yh; m.xl = xl; m.xh = xh;
+    m.fdW = make_fastdiv((uint32_t)W);
+    hipLaunchKernelGGL(sf_pack_clip_u8_mix_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
+    return check_launch("pack_clip_u8_mix");
+}
+extern "C" int sf_mix_targets(const int64_t* labels, int32_t B, int32_t K, float on_value, float off_value, float lam,
+                              float one_minus_lam, float* out, sf_stream_t stream) {
+    REQUIRE(labels && out, "sf_mix_targets: null pointer");
+    REQUIRE(B > 0 && K > 0 && (int64_t)B * K < (1ll << 31), "sf_mix_targets: bad shape");
+    MixTargetsParams p;
+    p.labels = labels; p.B = B; p.K = K; p.on = on_value; p.off = off_value; p.lam = lam; p.oml = one_minus_lam; p.out = out;
+    p.total = (int64_t)B * K;
+    p.fdK = make_fastdiv((uint32_t)K);
+    hipLaunchKernelGGL(sf_mix_targets_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("mix_targets");
 }
 
 static int row_scale_add_impl(const void* x, int32_t ldx, const float* scale, int64_t rows_per_sample, const void* resid,

@@ -28,10 +28,14 @@ def pathway_frame_indices(cfg, num_frames):
                               f"{cfg.MODEL.SINGLE_PATHWAY_ARCH + cfg.MODEL.MULTI_PATHWAY_ARCH}")
 
 
-def pack_pathways_u8(frames, cfg, out=None):
+def pack_pathways_u8(frames, cfg, out=None, mix=None):
     """frames: uint8 (N, T, H, W, 3) device tensor (decoded, sampled, cropped).  Returns the model input list: one
     channels-last fp16 tensor per pathway in the W-pair view (N, 8, T', H, W/2), tagged so that the stems use it as is.
-    ``out``: tensors of a previous call (e.g. the static input buffers of a captured step.TrainStep) to write into."""
+    ``out``: tensors of a previous call (e.g. the static input buffers of a captured step.TrainStep) to write into.
+    ``mix``: a ``mixup.MixParams`` (``MixUp.sample_params``): MixUp / CutMix of the batch, applied in fp32 between the
+    normalisation and the 16-bit rounding -- what the reference's ``mixup_fn`` does to the fp32 clip.  It applies to pathway 0
+    ONLY: the reference mixes ``inputs[0]`` and nothing else (tools/train_net.py:109-111), so the Fast pathway of a SlowFast
+    model stays unmixed.  ``mix=None`` (or a draw with lam == 1.0) is the unmixed kernel."""
     assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3 and frames.shape[3] % 2 == 0
     frames = frames.contiguous()
     N, T, H, W, _ = frames.shape
@@ -46,9 +50,17 @@ def pack_pathways_u8(frames, cfg, out=None):
             base = dst[i].permute(0, 2, 3, 4, 1)
             assert tuple(base.shape) == (N, Tout, H, W // 2, 8) and base.is_contiguous() and base.dtype == _f16, \
                 "out[i] must be a tensor a previous pack_pathways_u8 call returned for the same clip geometry"
-        get_lib().call("sf_pack_clip_u8", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1], mean[2],
-                       std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(),
-                       ops._stream(frames), work=dict(bytes=3.0 * N * Tout * H * W + 2.0 * base.numel()))
+        if i == 0 and mix is not None and mix.lam != 1.0:
+            lam = float(mix.lam)
+            yl, yh, xl, xh = mix.box if mix.use_cutmix else (0, 0, 0, 0)
+            get_lib().call("sf_pack_clip_u8_mix", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1],
+                           mean[2], std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(),
+                           int(bool(mix.use_cutmix)), lam, 1.0 - lam, int(yl), int(yh), int(xl), int(xh), ops._stream(frames),
+                           work=dict(bytes=(3.0 if mix.use_cutmix else 6.0) * N * Tout * H * W + 2.0 * base.numel()))
+        else:
+            get_lib().call("sf_pack_clip_u8", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1], mean[2],
+                           std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(),
+                           ops._stream(frames), work=dict(bytes=3.0 * N * Tout * H * W + 2.0 * base.numel()))
         x = base.permute(0, 4, 1, 2, 3)
         x._sf_wpairs = True                 # already the operand layout of engine.StemConvUnit
         out.append(x)

@@ -189,6 +189,16 @@ class TrainStep:
         stats = torch.zeros(4, dtype=torch.float32, device=logits.device)
         stats[0] = self._loss.float()
         stats[1] = self.grad_norm.float() if torch.is_tensor(self.grad_norm) else float(self.grad_norm or 0.0)
+        if labels is not None and labels.dim() == 2 and labels.is_floating_point() and logits.dim() == 2 \
+                and labels.shape == logits.shape and labels.shape[1] >= 2:
+            # soft labels of mixup.MixUp (tools/train_net.py:174-190): the two largest labels name the two mixed classes; the
+            # prediction of the second is added to the first's and zeroed, and the first counts as the label.  Device ops only.
+            top2 = labels.topk(2, dim=1, largest=True, sorted=True).indices
+            rows = torch.arange(labels.shape[0], device=labels.device)
+            logits = logits.detach().to(torch.float32, copy=True)
+            logits[rows, top2[:, 0]] += logits[rows, top2[:, 1]]
+            logits[rows, top2[:, 1]] = 0.0
+            labels = top2[:, 0]
         if labels is not None and labels.dim() == 1 and logits.dim() == 2:
             k = min(5, logits.shape[1])
             top = logits.float().topk(k, dim=1).indices
