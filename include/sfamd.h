@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 25
+#define SF_ABI_VERSION 26
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -413,6 +413,35 @@ int sf_pack_clip_u8_mix(const void* frames, int32_t N, int32_t Tin, int32_t H, i
  * s / K, s = label smoothing).  labels int64 [B] on the device, out fp32 [B][K] (may be a step's static label buffer). */
 int sf_mix_targets(const int64_t* labels, int32_t B, int32_t K, float on_value, float off_value, float lam, float one_minus_lam,
                    float* out, sf_stream_t stream);
+/* Random erasing of the batch (ABI 26) -- replaces RandomErasing.__call__ on the normalised host clip
+ * (slowfast/datasets/random_erasing.py, called at datasets/kinetics.py:437-447 before pack_pathway_output).  The boxes are drawn
+ * on the host and arrive as one table of int32 words, given twice: table_host is validated and sizes the grid, table_dev (the
+ * same words in device memory) is what the kernels read.  Layout: nrows rows of 12 words
+ *   n, t0, t1, top, left, h, w, key_lo, key_hi, colour word offset, end, 0
+ * (sample, frames [t0, t1), rows [top, top + h), columns [left, left + w), Philox key, offset of the row's (t1 - t0) x C colours
+ * from the table start, first row of the next sample), the rows of a sample adjacent in draw order and samples ascending; then
+ * N + 1 words first_row[n]; then the colours as float bits.  Where rows of a sample overlap the LAST one decides an element.
+ * mode 0 (const) writes 0.0f, 1 (rand) the row's colour of (frame, channel), 2 (pixel) a standard normal that depends on
+ * (key, idx) only, idx = ((c * T + t) * H + y) * W + x: Philox4x32-10 with the row's key and counter (idx >> 2, 0, 0, 0), whose
+ * outputs r0..r3 serve elements idx & 3 = 0..3 through Box-Muller on u = r * 2^-32 + 2^-33:
+ * z0 = sqrt(-2 ln u(r0)) sin(2 pi u(r1)), z1 = sqrt(-2 ln u(r0)) cos(2 pi u(r1)), z2 / z3 likewise from (r2, r3).
+ * Kernel launches only.
+ *
+ * sf_erase_clip_f32: dense fp32 clip [N][C][T][H][W].  dst == src erases in place (only erased elements are written, nothing is
+ *   read, a table without boxes launches nothing); any other dst must not overlap src and receives the whole erased clip. */
+int sf_erase_clip_f32(const float* src, float* dst, int32_t N, int32_t C, int32_t T, int32_t H, int32_t W, int32_t mode,
+                      const int32_t* table_host, const int32_t* table_dev, int32_t nrows, int32_t table_words,
+                      sf_stream_t stream);
+/* sf_pack_clip_u8 with erasing, then MixUp / CutMix, in fp32 BETWEEN the normalisation and the rounding to the 16-bit storage
+ * type: frame n and its mixing partner N-1-n are each normalised as sf_pack_clip_u8 does and erased with their own rows
+ * (C = 3, T = Tin, c and t are the SOURCE channel and frame: before the channel reversal and t_index), blended as
+ * sf_pack_clip_u8_mix does, rounded once.  table_host == table_dev == NULL erases nothing; mix_mode -1 mixes nothing, 0 / 1 as
+ * the mode of sf_mix_clip_f32. */
+int sf_pack_clip_u8_aug(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index, int32_t Tout,
+                        float mean0, float mean1, float mean2, float std0, float std1, float std2, int32_t reverse, void* out,
+                        int32_t erase_mode, const int32_t* table_host, const int32_t* table_dev, int32_t nrows,
+                        int32_t table_words, int32_t mix_mode, float lam, float one_minus_lam, int32_t yl, int32_t yh,
+                        int32_t xl, int32_t xh, sf_stream_t stream);
 /* Stochastic depth -- replaces drop_path() (slowfast/models/common.py:46-59) at the two residual additions of
  * MultiScaleBlock (attention.py:500-510): y[m] = (resid ? resid[m] : 0) + scale[m / rows_per_sample] * x[m], with
  * scale[b] = floor(keep_prob + u_b) / keep_prob sampled by the caller.  Rows are fp16 [M][C], C % 8 == 0. */

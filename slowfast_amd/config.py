@@ -120,6 +120,8 @@ _DEFAULTS = {
     # slowfast/config/defaults.py:239-257
     "MIXUP": {"ENABLE": False, "ALPHA": 0.8, "CUTMIX_ALPHA": 1.0, "PROB": 1.0, "SWITCH_PROB": 0.5,
               "LABEL_SMOOTH_VALUE": 0.1},
+    # slowfast/config/defaults.py:179-208 (the keys random_erasing.construct_random_erasing reads)
+    "AUG": {"ENABLE": False, "RE_PROB": 0.25, "RE_MODE": "pixel", "RE_COUNT": 1, "RE_SPLIT": False},
     "NUM_GPUS": 1, "NUM_SHARDS": 1, "SHARD_ID": 0, "RNG_SEED": 1, "LOG_MODEL_INFO": True, "DIST_BACKEND": "nccl",
     "OUTPUT_DIR": ".",
 }

@@ -16,6 +16,7 @@
 #include "sf_roi.h"
 #include "sf_optim.h"
 #include "sf_mixup.h"
+#include "sf_erase.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2566,6 +2567,99 @@ extern "C" int sf_mix_targets(const int64_t* labels, int32_t B, int32_t K, float
     p.fdK = make_fastdiv((uint32_t)K);
     hipLaunchKernelGGL(sf_mix_targets_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("mix_targets");
+}
+
+// ================================================================================================
+// Random erasing of the batch (sf_erase.h; replaces RandomErasing.__call__ on the host clip, datasets/kinetics.py:437-447).
+// The draw arrives as one table (layout: sf_erase.h); the HOST copy is validated and sizes the grid, the kernels read the
+// device copy.  Kernel launches only.
+static int check_erase_table(const char* who, const int32_t* th, int32_t nrows, int32_t words, int32_t mode, int32_t N,
+                             int32_t C, int32_t T, int32_t H, int32_t W, int64_t* max_items) {
+    REQUIRE(mode == SF_ERASE_CONST || mode == SF_ERASE_RAND || mode == SF_ERASE_PIXEL,
+            "%s: erase mode must be 0 (const), 1 (rand) or 2 (pixel)", who);
+    REQUIRE(th && nrows >= 0 && nrows < 65536, "%s: null erase table or more than 65535 rows", who);
+    const int64_t head = (int64_t)nrows * SF_ERASE_ROW_WORDS + N + 1;
+    REQUIRE(words >= head, "%s: erase table of %d words is shorter than %d rows + %d + 1 sample offsets", who, words, nrows, N);
+    const int32_t* first = th + (int64_t)nrows * SF_ERASE_ROW_WORDS;
+    REQUIRE(first[0] == 0 && first[N] == nrows, "%s: erase table sample offsets must run from 0 to the row count", who);
+    int64_t most = 0;
+    for (int n = 0; n < N; ++n) {
+        REQUIRE(first[n] <= first[n + 1], "%s: erase table sample offsets must ascend", who);
+        for (int r = first[n]; r < first[n + 1]; ++r) {
+            const int32_t* p = th + (int64_t)r * SF_ERASE_ROW_WORDS;
+            REQUIRE(p[0] == n && p[10] == first[n + 1], "%s: erase row %d is not filed under its sample", who, r);
+            REQUIRE(0 <= p[1] && p[1] <= p[2] && p[2] <= T && p[3] >= 0 && p[5] >= 0 && p[3] <= H - p[5] && p[4] >= 0 && p[6] >= 0
+                    && p[4] <= W - p[6],
+                    "%s: erase row %d (frames [%d, %d), rows [%d, %d), columns [%d, %d)) lies outside the %d x %d x %d clip", who,
+                    r, p[1], p[2], p[3], p[3] + p[5], p[4], p[4] + p[6], T, H, W);
+            if (mode == SF_ERASE_RAND)
+                REQUIRE(p[9] >= head && (int64_t)p[9] + (int64_t)(p[2] - p[1]) * C <= words,
+                        "%s: colours of erase row %d lie outside the table", who, r);
+            const int64_t items = (int64_t)C * (p[2] - p[1]) * p[5] * ((p[6] + 2) / 4 + 1);
+            if (p[6] > 0 && items > most) most = items;
+        }
+    }
+    *max_items = most;
+    return 0;
+}
+extern "C" int sf_erase_clip_f32(const float* src, float* dst, int32_t N, int32_t C, int32_t T, int32_t H, int32_t W,
+                                 int32_t mode, const int32_t* table_host, const int32_t* table_dev, int32_t nrows,
+                                 int32_t table_words, sf_stream_t stream) {
+    REQUIRE(src && dst && table_dev, "sf_erase_clip_f32: null pointer");
+    REQUIRE(N > 0 && N < 65536 && C > 0 && T > 0 && H > 0 && W > 0, "sf_erase_clip_f32: bad shape");
+    EraseClipParams p;
+    memset(&p, 0, sizeof(p));
+    p.S = (int64_t)C * T * H * W;
+    REQUIRE(p.S < (1ll << 30), "sf_erase_clip_f32: more than 2^30 elements per sample");
+    REQUIRE((uintptr_t)src % 4 == 0 && (uintptr_t)dst % 4 == 0, "sf_erase_clip_f32: buffers must be 4-byte aligned");
+    const bool inplace = (const float*)dst == src;
+    REQUIRE(inplace || dst + (int64_t)N * p.S <= src || src + (int64_t)N * p.S <= dst,
+            "sf_erase_clip_f32: dst must be src (in place) or must not overlap it");
+    int64_t most = 0;
+    if (check_erase_table("sf_erase_clip_f32", table_host, nrows, table_words, mode, N, C, T, H, W, &most)) return -1;
+    p.src = src; p.dst = dst; p.tab = table_dev; p.first_row = table_dev + (int64_t)nrows * SF_ERASE_ROW_WORDS;
+    p.N = N; p.C = C; p.T = T; p.H = H; p.W = W; p.mode = mode;
+    if (inplace) {
+        if (most == 0) return 0;                            // nothing to erase: nothing is launched
+        hipLaunchKernelGGL(sf_erase_inplace_kernel, dim3(mix_grid_x(most, nrows), nrows), dim3(SF_THREADS), 0,
+                           (hipStream_t)stream, p);
+        return check_launch("erase_clip_f32");
+    }
+    p.items = (p.S + 3) / 4;
+    hipLaunchKernelGGL(sf_erase_copy_kernel, dim3(mix_grid_x(p.items, N), N), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("erase_clip_f32 (copy)");
+}
+extern "C" int sf_pack_clip_u8_aug(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
+                                   int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                                   int32_t reverse, void* out, int32_t erase_mode, const int32_t* table_host,
+                                   const int32_t* table_dev, int32_t nrows, int32_t table_words, int32_t mix_mode, float lam,
+                                   float one_minus_lam, int32_t yl, int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream) {
+    REQUIRE(frames && out, "sf_pack_clip_u8_aug: null pointer");
+    REQUIRE(N > 0 && Tin > 0 && Tout > 0 && H > 0 && W > 0 && W % 2 == 0, "sf_pack_clip_u8_aug: bad shape (W must be even)");
+    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_pack_clip_u8_aug: zero std");
+    REQUIRE(mix_mode >= -1 && mix_mode <= 1, "sf_pack_clip_u8_aug: mix mode must be -1 (none), 0 (mixup) or 1 (cutmix)");
+    if (mix_mode >= 0 && check_mix_box("sf_pack_clip_u8_aug", mix_mode, H, W, yl, yh, xl, xh)) return -1;
+    REQUIRE((table_host == nullptr) == (table_dev == nullptr), "sf_pack_clip_u8_aug: the erase table needs both of its copies");
+    int64_t most = 0;
+    if (table_host && check_erase_table("sf_pack_clip_u8_aug", table_host, nrows, table_words, erase_mode, N, 3, Tin, H, W, &most))
+        return -1;
+    PackClipAugParams m;
+    memset(&m, 0, sizeof(m));
+    PackClipParams& p = m.k;
+    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = Tin; p.Tout = Tout; p.HW = (int64_t)H * W;
+    p.t_index = t_index; p.reverse = reverse; p.out = (f16*)out;
+    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
+    p.total = (int64_t)N * Tout * p.HW;
+    REQUIRE(p.total < (1ll << 31) && (int64_t)N * Tin * p.HW < (1ll << 40), "sf_pack_clip_u8_aug: too many pixels");
+    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)Tout);
+    m.H = H; m.W = W; m.mix = mix_mode; m.lam = lam; m.oml = one_minus_lam;
+    if (mix_mode == 1) { m.yl = yl; m.yh = yh; m.xl = xl; m.xh = xh; }
+    m.erase_mode = erase_mode;
+    m.tab = (table_dev && nrows > 0) ? table_dev : nullptr;
+    m.first_row = m.tab ? table_dev + (int64_t)nrows * SF_ERASE_ROW_WORDS : nullptr;
+    m.fdW = make_fastdiv((uint32_t)W);
+    hipLaunchKernelGGL(sf_pack_clip_u8_aug_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
+    return check_launch("pack_clip_u8_aug");
 }
 
 static int row_scale_add_impl(const void* x, int32_t ldx, const float* scale, int64_t rows_per_sample, const void* resid,

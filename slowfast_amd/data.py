@@ -28,19 +28,34 @@ def pathway_frame_indices(cfg, num_frames):
                               f"{cfg.MODEL.SINGLE_PATHWAY_ARCH + cfg.MODEL.MULTI_PATHWAY_ARCH}")
 
 
-def pack_pathways_u8(frames, cfg, out=None, mix=None):
+def pack_pathways_u8(frames, cfg, out=None, mix=None, erase=None):
     """frames: uint8 (N, T, H, W, 3) device tensor (decoded, sampled, cropped).  Returns the model input list: one
     channels-last fp16 tensor per pathway in the W-pair view (N, 8, T', H, W/2), tagged so that the stems use it as is.
     ``out``: tensors of a previous call (e.g. the static input buffers of a captured step.TrainStep) to write into.
     ``mix``: a ``mixup.MixParams`` (``MixUp.sample_params``): MixUp / CutMix of the batch, applied in fp32 between the
     normalisation and the 16-bit rounding -- what the reference's ``mixup_fn`` does to the fp32 clip.  It applies to pathway 0
     ONLY: the reference mixes ``inputs[0]`` and nothing else (tools/train_net.py:109-111), so the Fast pathway of a SlowFast
-    model stays unmixed.  ``mix=None`` (or a draw with lam == 1.0) is the unmixed kernel."""
+    model stays unmixed.  ``mix=None`` (or a draw with lam == 1.0) is the unmixed kernel.
+    ``erase``: a ``random_erasing.EraseTable`` (``RandomErasing.sample_batch(N, (T, 3, H, W))``): random erasing of the
+    normalised clip, in fp32 before the mixing and the rounding.  It applies to EVERY pathway -- the reference erases in the
+    dataset before ``pack_pathway_output`` (datasets/kinetics.py:437-449) -- and sample ``i`` and its mixing partner
+    ``N-1-i`` are each erased with their own rows before they are blended.  Erased values are indexed by the source frame and
+    by the channel in DATA.MEAN order, so the Slow pathway stays the ``index_select`` of the Fast one and
+    DATA.REVERSE_INPUT_CHANNEL permutes them with the image.  ``erase=None`` (or a table without rows) reaches the kernels
+    above unchanged."""
     assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3 and frames.shape[3] % 2 == 0
     frames = frames.contiguous()
     N, T, H, W, _ = frames.shape
     mean, std = [float(v) for v in cfg.DATA.MEAN], [float(v) for v in cfg.DATA.STD]
     dst, out = out, []
+    tab = None
+    if erase is not None and len(erase.rows):
+        from . import random_erasing
+        if tuple(erase.shape) != (T, 3, H, W):
+            raise _sflib.SfError("pack_pathways_u8: the erase table was drawn for (T, C, H, W) = %s, the frames are %s" % (
+                tuple(erase.shape), (T, 3, H, W)))
+        ops._stream(frames)
+        tab = random_erasing.upload_table(erase, N, frames.device) + (random_erasing.MODES[erase.mode],)
     for i, idx in enumerate(pathway_frame_indices(cfg, T)):
         Tout = T if idx is None else int(idx.numel())
         idx_dev = None if idx is None else idx.to(device=frames.device, dtype=torch.int32).contiguous()
@@ -50,7 +65,19 @@ def pack_pathways_u8(frames, cfg, out=None, mix=None):
             base = dst[i].permute(0, 2, 3, 4, 1)
             assert tuple(base.shape) == (N, Tout, H, W // 2, 8) and base.is_contiguous() and base.dtype == _f16, \
                 "out[i] must be a tensor a previous pack_pathways_u8 call returned for the same clip geometry"
-        if i == 0 and mix is not None and mix.lam != 1.0:
+        mixing = i == 0 and mix is not None and mix.lam != 1.0
+        if tab is not None:
+            host, dev, rows, emode = tab
+            lam = float(mix.lam) if mixing else 1.0
+            yl, yh, xl, xh = mix.box if mixing and mix.use_cutmix else (0, 0, 0, 0)
+            get_lib().call("sf_pack_clip_u8_aug", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1],
+                           mean[2], std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(), emode,
+                           host.ctypes.data, dev.data_ptr(), rows, int(host.size),
+                           int(bool(mix.use_cutmix)) if mixing else -1, lam, 1.0 - lam, int(yl), int(yh), int(xl), int(xh),
+                           ops._stream(frames),
+                           work=dict(bytes=(6.0 if mixing and not mix.use_cutmix else 3.0) * N * Tout * H * W
+                                     + 2.0 * base.numel()))
+        elif mixing:
             lam = float(mix.lam)
             yl, yh, xl, xh = mix.box if mix.use_cutmix else (0, 0, 0, 0)
             get_lib().call("sf_pack_clip_u8_mix", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1],
