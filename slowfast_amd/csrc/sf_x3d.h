@@ -77,6 +77,13 @@ __global__ __launch_bounds__(SF_THREADS) void sf_sample_sum_kernel(SampleSumPara
                     const float t = (float)d[e] * act_grad(gt[e] * u, p.swish);
                     a[e] += t * u;
                     o[e] = (f16)(t * gt[e]);
+                }
+                // b and a2 must be sums of the 16-bit values that are STORED.  Left to itself hipcc rounds the product twice over:
+                // v_fma_mixlo_f16 (one rounding) feeds the sums, v_mul_f32 + v_cvt_pk_f16_f32 (two roundings) the store, and the
+                // two differ by an ulp wherever the fp32 product lands on a 16-bit tie
+                SF_CONSUME_V(o);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
                     b[e] += (float)o[e];
                     a2[e] += (float)o[e] * (float)v[e];
                 }

@@ -180,6 +180,34 @@ class DwUnit:
         return cl5d(dx2d, x.shape[0], x.shape[1], g.thw)
 
 
+def gate_bn_backward(t, yb, sb, gate, se, ysum, dzb):
+    """Backward of b_bn -> [SE gate] -> Swish/ReLU of an X3DTransform ``t``: the gradient ``dzb`` of the activation's output ->
+    the gradient of the BatchNorm's input ``yb``; writes the b_bn and SE parameter gradients.  ``se`` = (squeezed means, hidden)
+    of the forward, ``ysum`` the per-sample channel sums of yb the forward took from the statistics table (or None)."""
+    dmean = None
+    if t._se is not None and ysum is not None and engine.BN_FUSE_REDUCE and GATE_ONE_PASS:
+        # SE block, ONE pass over (yb, dzb) instead of three (sf_gate_grad, sf_gate_act_bwd, sf_bn_bwd_reduce): the squeeze
+        # term dmean[n][c] / S of du is a per-sample constant, so it is never stored -- the pass leaves du0 and the
+        # per-sample sums; b_bn's reduction follows from them and from the per-sample sums of yb the forward kept
+        # (sum du = sum_n (sum du0_n + dmean_n), sum du * y = sum_n (sum (du0 y)_n + dmean_n / S * sum y_n)), and the apply
+        # pass adds the constant back: dyb = k1 * (du0 + dmean_n / S) + k2 + k3 * yb.
+        du, sums = gate_bwd_sums(yb, sb.scale, sb.shift, gate, t._swish_inner, dzb)
+        dmean = t._se.gate_bwd(se[0], se[1], gate, sums[:, 0].contiguous())
+        add = dmean * (float(yb.shape[0]) / float(ops.rows(yb)))                    # dmean / S, [N, C]
+        part_b = torch.stack(((sums[:, 1] + dmean).sum(0), (sums[:, 2] + add * ysum).sum(0))).unsqueeze(0).contiguous()
+        dyb = t._b_bn.backward(du, yb, sb, part=part_b, sample_add=add.contiguous())
+    else:
+        if t._se is not None:
+            dgate = gate_grad(yb, sb.scale, sb.shift, dzb, gate, t._swish_inner)
+            dmean = t._se.gate_bwd(se[0], se[1], gate, dgate)
+        if engine.BN_FUSE_REDUCE and GATE_BN_FUSE:  # the reduction of b_bn's backward rides on the gate / Swish backward pass
+            du, part_b = gate_act_bwd(yb, sb.scale, sb.shift, gate, t._swish_inner, dzb, dmean, bn_part=True)
+        else:
+            du, part_b = gate_act_bwd(yb, sb.scale, sb.shift, gate, t._swish_inner, dzb, dmean), None
+        dyb = t._b_bn.backward(du, yb, sb, part=part_b)
+    return dyb
+
+
 # ------------------------------------------------------------------------------------------------
 class X3DStemFn(torch.autograd.Function):
     """conv_xy (1,3,3)/(1,2,2) -> depthwise (5,1,1) -> BN -> ReLU (stem_helper.py:279-285)."""
@@ -275,28 +303,7 @@ class X3DBlockFn(torch.autograd.Function):
         if P is not None:
             dy1 = P.bn_backward(dout, sv["y1"], sv["s1"], zmask=bits)
         dzb = C.backward(sv["zb"], None, dyc, need_dx=True)
-        yb, sb, gate = sv["yb"], sv["sb"], sv["gate"]
-        dmean = None
-        if t._se is not None and sv["ysum"] is not None and engine.BN_FUSE_REDUCE and GATE_ONE_PASS:
-            # SE block, ONE pass over (yb, dzb) instead of three (sf_gate_grad, sf_gate_act_bwd, sf_bn_bwd_reduce): the squeeze
-            # term dmean[n][c] / S of du is a per-sample constant, so it is never stored -- the pass leaves du0 and the
-            # per-sample sums; b_bn's reduction follows from them and from the per-sample sums of yb the forward kept
-            # (sum du = sum_n (sum du0_n + dmean_n), sum du * y = sum_n (sum (du0 y)_n + dmean_n / S * sum y_n)), and the apply
-            # pass adds the constant back: dyb = k1 * (du0 + dmean_n / S) + k2 + k3 * yb.
-            du, sums = gate_bwd_sums(yb, sb.scale, sb.shift, gate, t._swish_inner, dzb)
-            dmean = t._se.gate_bwd(sv["se"][0], sv["se"][1], gate, sums[:, 0].contiguous())
-            add = dmean * (float(yb.shape[0]) / float(ops.rows(yb)))                    # dmean / S, [N, C]
-            part_b = torch.stack(((sums[:, 1] + dmean).sum(0), (sums[:, 2] + add * sv["ysum"]).sum(0))).unsqueeze(0).contiguous()
-            dyb = t._b_bn.backward(du, yb, sb, part=part_b, sample_add=add.contiguous())
-        else:
-            if t._se is not None:
-                dgate = gate_grad(yb, sb.scale, sb.shift, dzb, gate, t._swish_inner)
-                dmean = t._se.gate_bwd(sv["se"][0], sv["se"][1], gate, dgate)
-            if engine.BN_FUSE_REDUCE and GATE_BN_FUSE:  # the reduction of b_bn's backward rides on the gate / Swish backward pass
-                du, part_b = gate_act_bwd(yb, sb.scale, sb.shift, gate, t._swish_inner, dzb, dmean, bn_part=True)
-            else:
-                du, part_b = gate_act_bwd(yb, sb.scale, sb.shift, gate, t._swish_inner, dzb, dmean), None
-            dyb = t._b_bn.backward(du, yb, sb, part=part_b)
+        dyb = gate_bn_backward(t, sv["yb"], sv["sb"], sv["gate"], sv["se"], sv["ysum"], dzb)
         dza = t._b.backward(sv["za"], dyb, need_dx=True)
         dya = A.bn_backward(dza, sv["ya"], sv["sa"], relu_self=True)
         prev = ctx.prev_bn if need_dx else None

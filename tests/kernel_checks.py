@@ -277,6 +277,48 @@ def check_pool(device, shape, seed=0):
     assert_close("pool_bwd", cl_to_host(gm), gref, 2 * F16_EPS)
 
 
+def check_pool3d(device, shape, k, ld_extra=0, ties=False, seed=0):
+    """nonlocal_block.pool3d_fwd / pool3d_bwd (MaxPool3d with kernel = stride, no padding) against F.max_pool3d in fp64 and its
+    autograd.  The maximum is exact, and with distinct window elements the backward is a pure scatter, so both are compared VALUE
+    FOR VALUE; odd extents are floored and the left-over rows / columns get a zero gradient.  The input is a random permutation of
+    T * H * W distinct multiples of 1/16 per (sample, channel), all of them representable in either storage type, so no window holds
+    two equal elements (asserted).  ``ties``: a constant input -- every window sends its whole gradient to exactly one element, the
+    first in (t, h, w) scan order as in torch, and the gradient sums per channel are preserved.  ``ld_extra``: a wider row pitch of
+    the input, its padding filled with NaN."""
+    from slowfast_amd.nonlocal_block import pool3d_bwd, pool3d_fwd
+    g = torch.Generator().manual_seed(seed)
+    N, C, T, H, W = shape
+    P = T * H * W
+    assert P <= 256
+    if ties:
+        x = torch.full(shape, 0.75)
+    else:
+        x = ((torch.rand((N, C, P), generator=g).argsort(-1) - P // 2).float() / 16).view(shape)
+        assert torch.equal(x.to(ACT).float(), x)
+        win = x[:, :, : T // k[0] * k[0], : H // k[1] * k[1], : W // k[2] * k[2]]
+        win = win.unfold(2, k[0], k[0]).unfold(3, k[1], k[1]).unfold(4, k[2], k[2]).reshape(N, C, -1, k[0] * k[1] * k[2])
+        srt = win.sort(-1).values
+        assert bool((srt[..., 1:] > srt[..., :-1]).all()), "two equal elements in one pool window"
+    xr = x.double().requires_grad_(True)
+    ref = F.max_pool3d(xr, tuple(k), tuple(k))
+    dout = torch.randn(ref.shape, generator=g).to(ACT).float()
+    ref.backward(dout.double())
+    base = torch.full((N, T, H, W, C + ld_extra), float("nan"), dtype=ACT, device=device)
+    xc = base[..., :C].permute(0, 4, 1, 2, 3)
+    xc.copy_(x.to(ACT))
+    out, arg = pool3d_fwd(xc, tuple(k))
+    assert tuple(out.shape) == tuple(ref.shape)
+    assert torch.equal(cl_to_host(out).double(), ref.detach()), "pool3d_fwd"
+    dx = cl_to_host(pool3d_bwd(host_to_cl(dout, device), arg, tuple(shape), tuple(k))).double()
+    assert torch.equal(dx, xr.grad), "pool3d_bwd"
+    if ties:
+        To, Ho, Wo = ref.shape[2:]
+        first = torch.zeros(shape, dtype=torch.float64)
+        first[:, :, : To * k[0]: k[0], : Ho * k[1]: k[1], : Wo * k[2]: k[2]] = dout.double()
+        assert torch.equal(dx, first), "a tie goes to the first element of the window in (t, h, w) scan order"
+        assert torch.equal(dx.sum((0, 2, 3, 4)), dout.double().sum((0, 2, 3, 4)))      # sums of 16-bit values: exact in fp64
+
+
 def check_head_mean(device, shape, seed=0):
     """heads._GlobalMeanFn (sf_tmean_fwd as [8][rows / 8] partial means + sf_tmean_bwd as a broadcast) against the AvgPool3d over
     the whole extent of the reference head (head_helper.py:293-300) on the same 16-bit operand: fp32 sums in another order."""

@@ -46,8 +46,8 @@ def test_bf16_builds_identify_themselves():
 
 def test_bf16_kernels_and_blocks_hostsim():
     """Kernel, token-kernel, implicit-GEMM-variant and block-level checks on the host simulator's bf16 build."""
-    _run_pytest_bf16(["tests/test_kernels_hostsim.py", "tests/test_tokens_hostsim.py", "tests/test_igemm2_hostsim.py",
-                      "tests/test_blocks_hostsim.py", "-m", "not gpu"], timeout=1500)
+    _run_pytest_bf16(["tests/test_kernels_hostsim.py", "tests/test_x3d_kernels_hostsim.py", "tests/test_tokens_hostsim.py",
+                      "tests/test_igemm2_hostsim.py", "tests/test_blocks_hostsim.py", "-m", "not gpu"], timeout=1500)
 
 
 def test_bf16_models_hostsim():

@@ -6,7 +6,7 @@ import sys
 import pytest
 
 from tests import kernel_checks as kc
-from tests.test_kernels_hostsim import CONV_CASES
+from tests.test_kernels_hostsim import CONV_CASES, POOL3D_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -181,6 +181,16 @@ def test_bn_chain(gpu, shape, relu, residual):
 def test_pool(gpu):
     kc.check_pool(gpu, (1, 8, 2, 9, 9))
     kc.check_pool(gpu, (2, 64, 2, 56, 56))
+
+
+@pytest.mark.parametrize("shape,k,ld_extra", POOL3D_CASES)
+def test_pool3d(gpu, shape, k, ld_extra):
+    kc.check_pool3d(gpu, shape, k, ld_extra)
+
+
+def test_pool3d_ties_go_to_the_first_element(gpu):
+    kc.check_pool3d(gpu, (1, 40, 4, 9, 7), (2, 2, 2), ties=True)
+    kc.check_pool3d(gpu, (2, 8, 2, 4, 4), (1, 2, 2), ties=True)
 
 
 def test_head_mean(gpu):

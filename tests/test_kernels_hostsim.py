@@ -105,6 +105,23 @@ def test_pool(sim):
     kc.check_pool(sim, (2, 16, 1, 8, 8))
 
 
+POOL3D_CASES = [
+    ((2, 8, 2, 4, 4), (1, 2, 2), 0),
+    ((1, 40, 4, 9, 7), (2, 2, 2), 0),        # odd extents are floored: the last row / column belongs to no window
+    ((2, 64, 3, 6, 6), (1, 2, 2), 8),        # wider row pitch of the input
+]
+
+
+@pytest.mark.parametrize("shape,k,ld_extra", POOL3D_CASES)
+def test_pool3d(sim, shape, k, ld_extra):
+    kc.check_pool3d(sim, shape, k, ld_extra)
+
+
+def test_pool3d_ties_go_to_the_first_element(sim):
+    kc.check_pool3d(sim, (1, 40, 4, 9, 7), (2, 2, 2), ties=True)
+    kc.check_pool3d(sim, (2, 8, 2, 4, 4), (1, 2, 2), ties=True)
+
+
 def test_head_mean(sim):
     kc.check_head_mean(sim, (2, 16, 2, 3, 4))
     kc.check_head_mean(sim, (1, 8, 4, 2, 2))
