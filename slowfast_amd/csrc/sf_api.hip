@@ -2191,6 +2191,8 @@ static int fill_softmax(SoftmaxParams& p, const sf_attn_desc* d, void* s, int32_
 extern "C" int sf_softmax_fwd(const sf_attn_desc* d, void* s, int32_t lds, float scale, const float* rq, sf_stream_t stream) {
     SoftmaxParams p;
     if (fill_softmax(p, d, s, lds, scale)) return -1;
+    // one lane per bias entry: the kernel stages a row's rq in s_rq[4][64]
+    REQUIRE(!rq || p.R <= 64, "sf_softmax_fwd: kH + kW + kT must be <= 64 with a rel-pos bias");
     p.rq = rq;
     int blocks = cdiv(p.rows, 4);
     if (blocks > 16384) blocks = 16384;
@@ -2205,6 +2207,7 @@ extern "C" int sf_softmax_bwd(const sf_attn_desc* d, void* dp, const void* prob,
     SoftmaxParams p;
     if (fill_softmax(p, d, dp, lds, scale)) return -1;
     REQUIRE(prob != nullptr, "sf_softmax_bwd: null pointer");
+    REQUIRE(!drq || p.R <= 64, "sf_softmax_bwd: kH + kW + kT must be <= 64 with a rel-pos bias");     // lane j < 64 owns drq[j]
     p.prob = (const f16*)prob; p.drq = drq;
     int blocks = cdiv(p.rows, 4);
     if (blocks > 16384) blocks = 16384;
