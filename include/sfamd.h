@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 26
+#define SF_ABI_VERSION 27
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -442,6 +442,35 @@ int sf_pack_clip_u8_aug(const void* frames, int32_t N, int32_t Tin, int32_t H, i
                         int32_t erase_mode, const int32_t* table_host, const int32_t* table_dev, int32_t nrows,
                         int32_t table_words, int32_t mix_mode, float lam, float one_minus_lam, int32_t yl, int32_t yh,
                         int32_t xl, int32_t xh, sf_stream_t stream);
+/* Spatial sampling of the batch (ABI 27) -- replaces utils.spatial_sampling on the normalised host clip
+ * (slowfast/datasets/utils.py:114-185, called at datasets/kinetics.py:410-435: short-side scale jitter or random resized crop,
+ * i.e. a bilinear F.interpolate of every frame, then a crop and a horizontal flip).  frames is uint8 [N][T][Hs][Ws][3], every
+ * sample padded to the batch's largest frame.  The draw arrives as one table of int32 words, given twice as the erase table is:
+ * crop_host is validated, crop_dev (the same words in device memory) is what the kernels read.  Layout: N rows of 12 words
+ *   src_h, src_w, win_y, win_x, win_h, win_w, res_h, res_w, off_y, off_x, flip, 0
+ * (valid frame size; the source window that is resized; the size it is resized to; the S x S crop inside the resized image;
+ * horizontal flip).  Every row must satisfy 0 < src <= (Hs, Ws), the window inside the valid size with positive lengths,
+ * 0 <= off <= res - S, flip 0 / 1, all sizes below 65536.  Output pixel (oy, ox), per axis in fp32, in this order:
+ *   r = o + off (x axis: o = S-1-ox when flip);  sc = (float)win_len / (float)res_len;  f = max(sc * (r + 0.5f) - 0.5f, 0);
+ *   i0 = (int)f;  l1 = f - i0;  l0 = 1 - l1;  i1 = i0 + (i0 < win_len - 1)
+ * with taps at win + i0 / i1 (i1 clamps to the WINDOW, not the frame), each normalised as sf_pack_clip_u8 does, then
+ * l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d), no contraction.  win_len == res_len gives the normalised source
+ * pixel bit for bit.  Kernel launches only.
+ *
+ * sf_sample_clip_u8: out is the dense fp32 clip [N][3][T][S][S] (channels in mean order) that sf_erase_clip_f32 and
+ *   sf_mix_clip_f32 take in place. */
+int sf_sample_clip_u8(const void* frames, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* crop_host,
+                      const int32_t* crop_dev, int32_t S, float mean0, float mean1, float mean2, float std0, float std1,
+                      float std2, float* out, sf_stream_t stream);
+/* sf_pack_clip_u8_aug with every sample -- and its mixing partner N-1-n, through ITS row -- sampled first: sample, erase, mix
+ * in fp32, one rounding to the 16-bit storage type into the N,Tout,S,S,4 W-pair buffer.  S must be even.  The erase table is
+ * the one of sf_pack_clip_u8_aug for the CROPPED clip (C = 3, T = Tin, H = W = S), the cutmix box lies in the S x S plane. */
+int sf_pack_clip_u8_sample(const void* frames, int32_t N, int32_t Tin, int32_t Hs, int32_t Ws, const int32_t* t_index,
+                           int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                           int32_t reverse, void* out, const int32_t* crop_host, const int32_t* crop_dev, int32_t S,
+                           int32_t erase_mode, const int32_t* table_host, const int32_t* table_dev, int32_t nrows,
+                           int32_t table_words, int32_t mix_mode, float lam, float one_minus_lam, int32_t yl, int32_t yh,
+                           int32_t xl, int32_t xh, sf_stream_t stream);
 /* Stochastic depth -- replaces drop_path() (slowfast/models/common.py:46-59) at the two residual additions of
  * MultiScaleBlock (attention.py:500-510): y[m] = (resid ? resid[m] : 0) + scale[m / rows_per_sample] * x[m], with
  * scale[b] = floor(keep_prob + u_b) / keep_prob sampled by the caller.  Rows are fp16 [M][C], C % 8 == 0. */

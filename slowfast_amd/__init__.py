@@ -13,4 +13,6 @@ from . import x3d  # noqa: F401,E402  (registers X3D, the x3d_stem and x3d_trans
 from .data import pack_pathways_u8  # noqa: F401,E402  (uint8 frames -> stem operand layout)
 from .mixup import MixUp, construct_mixup  # noqa: F401,E402  (MixUp / CutMix of the batch on the device)
 from .random_erasing import RandomErasing, ErasePlan, construct_random_erasing  # noqa: F401,E402  (random erasing on the device)
+from .spatial_sampling import (SpatialSampling, CropRow, CropTable, construct_spatial_sampling,  # noqa: F401,E402
+                               sample_clip)  # (scale jitter / crop / flip from uint8 on the device)
 from .losses import get_loss_func  # noqa: F401,E402

@@ -78,7 +78,7 @@ _DEFAULTS = {
     "BN": {"USE_PRECISE_STATS": False, "NUM_BATCHES_PRECISE": 200, "WEIGHT_DECAY": 0.0, "NORM_TYPE": "batchnorm",
            "NUM_SPLITS": 1, "NUM_SYNC_DEVICES": 1, "GLOBAL_SYNC": False},
     "TRAIN": {"ENABLE": True, "DATASET": "kinetics", "BATCH_SIZE": 64, "MIXED_PRECISION": False},
-    "TEST": {"ENABLE": True, "DATASET": "kinetics", "BATCH_SIZE": 8},
+    "TEST": {"ENABLE": True, "DATASET": "kinetics", "BATCH_SIZE": 8, "NUM_SPATIAL_CROPS": 3},
     "RESNET": {"TRANS_FUNC": "bottleneck_transform", "NUM_GROUPS": 1, "WIDTH_PER_GROUP": 64, "INPLACE_RELU": True,
                "STRIDE_1X1": False, "ZERO_INIT_FINAL_BN": False, "ZERO_INIT_FINAL_CONV": False, "DEPTH": 50,
                "NUM_BLOCK_TEMP_KERNEL": [[3], [4], [6], [3]], "SPATIAL_STRIDES": [[1], [2], [2], [2]],
@@ -94,7 +94,10 @@ _DEFAULTS = {
     "SLOWFAST": {"BETA_INV": 8, "ALPHA": 8, "FUSION_CONV_CHANNEL_RATIO": 2, "FUSION_KERNEL_SZ": 5},
     "DATA": {"NUM_FRAMES": 8, "SAMPLING_RATE": 8, "MEAN": [0.45, 0.45, 0.45], "INPUT_CHANNEL_NUM": [3, 3],
              "STD": [0.225, 0.225, 0.225], "TRAIN_CROP_SIZE": 224, "TEST_CROP_SIZE": 256,
-             "REVERSE_INPUT_CHANNEL": False},
+             "REVERSE_INPUT_CHANNEL": False,
+             # slowfast/config/defaults.py:696-737 (the keys spatial_sampling.construct_spatial_sampling reads)
+             "TRAIN_JITTER_SCALES": [256, 320], "TRAIN_JITTER_SCALES_RELATIVE": [], "TRAIN_JITTER_ASPECT_RELATIVE": [],
+             "TRAIN_JITTER_MOTION_SHIFT": False, "INV_UNIFORM_SAMPLE": False, "RANDOM_FLIP": True},
     "SOLVER": {"BASE_LR": 0.1, "MOMENTUM": 0.9, "DAMPENING": 0.0, "NESTEROV": True, "WEIGHT_DECAY": 1e-4,
                "OPTIMIZING_METHOD": "sgd", "ZERO_WD_1D_PARAM": False, "CLIP_GRAD_VAL": None,
                "CLIP_GRAD_L2NORM": None, "LAYER_DECAY": 1.0},

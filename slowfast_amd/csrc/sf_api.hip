@@ -17,6 +17,7 @@
 #include "sf_optim.h"
 #include "sf_mixup.h"
 #include "sf_erase.h"
+#include "sf_sample.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2663,6 +2664,90 @@ extern "C" int sf_pack_clip_u8_aug(const void* frames, int32_t N, int32_t Tin, i
     m.fdW = make_fastdiv((uint32_t)W);
     hipLaunchKernelGGL(sf_pack_clip_u8_aug_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
     return check_launch("pack_clip_u8_aug");
+}
+
+// ================================================================================================
+// Spatial sampling of the batch (sf_sample.h; replaces utils.spatial_sampling on the normalised host clip,
+// datasets/kinetics.py:410-435).  The draw arrives as one table with a row per sample (layout: sf_sample.h); the HOST copy is
+// validated, the kernels read the device copy.  Kernel launches only.
+static int check_crop_table(const char* who, const int32_t* th, int32_t N, int32_t Hs, int32_t Ws, int32_t S) {
+    REQUIRE(th, "%s: null crop table", who);
+    // (float)r must be exact and (win + i) * Ws * 3 stays far inside int64; the limit is what the coordinate rule assumes
+    REQUIRE(Hs > 0 && Ws > 0 && Hs < (1 << 16) && Ws < (1 << 16) && S > 0 && S < (1 << 16),
+            "%s: frame %d x %d / crop %d must be positive and below 65536", who, Hs, Ws, S);
+    for (int n = 0; n < N; ++n) {
+        const int32_t* c = th + (int64_t)n * SF_CROP_ROW_WORDS;
+        REQUIRE(c[0] > 0 && c[0] <= Hs && c[1] > 0 && c[1] <= Ws,
+                "%s: crop row %d: valid size %d x %d is not inside the %d x %d buffer", who, n, c[0], c[1], Hs, Ws);
+        REQUIRE(c[4] > 0 && c[5] > 0 && c[2] >= 0 && c[3] >= 0 && c[2] <= c[0] - c[4] && c[3] <= c[1] - c[5],
+                "%s: crop row %d: window rows [%d, %d) columns [%d, %d) lies outside the valid %d x %d", who, n, c[2],
+                c[2] + c[4], c[3], c[3] + c[5], c[0], c[1]);
+        REQUIRE(c[6] > 0 && c[7] > 0 && c[6] < (1 << 16) && c[7] < (1 << 16),
+                "%s: crop row %d: resized size %d x %d must be positive and below 65536", who, n, c[6], c[7]);
+        REQUIRE(c[8] >= 0 && c[9] >= 0 && c[8] <= c[6] - S && c[9] <= c[7] - S,
+                "%s: crop row %d: crop %d at (%d, %d) lies outside the resized %d x %d", who, n, S, c[8], c[9], c[6], c[7]);
+        REQUIRE(c[10] == 0 || c[10] == 1, "%s: crop row %d: flip must be 0 or 1", who, n);
+    }
+    return 0;
+}
+static void fill_sample_geom(SampleGeom& g, const int32_t* crop_dev, int32_t Hs, int32_t Ws, int32_t S) {
+    g.crop = crop_dev; g.Hs = Hs; g.Ws = Ws; g.S = S; g.fdS = make_fastdiv((uint32_t)S);
+}
+extern "C" int sf_sample_clip_u8(const void* frames, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* crop_host,
+                                 const int32_t* crop_dev, int32_t S, float mean0, float mean1, float mean2, float std0,
+                                 float std1, float std2, float* out, sf_stream_t stream) {
+    REQUIRE(frames && out && crop_dev, "sf_sample_clip_u8: null pointer");
+    REQUIRE(N > 0 && T > 0, "sf_sample_clip_u8: bad shape");
+    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_sample_clip_u8: zero std");
+    REQUIRE((uintptr_t)out % 4 == 0, "sf_sample_clip_u8: out must be 4-byte aligned");
+    if (check_crop_table("sf_sample_clip_u8", crop_host, N, Hs, Ws, S)) return -1;
+    SampleClipParams m;
+    memset(&m, 0, sizeof(m));
+    PackClipParams& p = m.k;
+    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = T; p.Tout = T; p.HW = (int64_t)S * S;
+    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
+    p.total = (int64_t)N * T * p.HW;
+    REQUIRE(p.total < (1ll << 31) && (int64_t)N * T * Hs * Ws < (1ll << 40), "sf_sample_clip_u8: too many pixels");
+    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)T);
+    fill_sample_geom(m.g, crop_dev, Hs, Ws, S);
+    m.dst = out;
+    hipLaunchKernelGGL(sf_sample_clip_u8_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
+    return check_launch("sample_clip_u8");
+}
+extern "C" int sf_pack_clip_u8_sample(const void* frames, int32_t N, int32_t Tin, int32_t Hs, int32_t Ws, const int32_t* t_index,
+                                      int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                                      int32_t reverse, void* out, const int32_t* crop_host, const int32_t* crop_dev, int32_t S,
+                                      int32_t erase_mode, const int32_t* table_host, const int32_t* table_dev, int32_t nrows,
+                                      int32_t table_words, int32_t mix_mode, float lam, float one_minus_lam, int32_t yl,
+                                      int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream) {
+    REQUIRE(frames && out && crop_dev, "sf_pack_clip_u8_sample: null pointer");
+    REQUIRE(N > 0 && Tin > 0 && Tout > 0, "sf_pack_clip_u8_sample: bad shape");
+    REQUIRE(S > 0 && S % 2 == 0, "sf_pack_clip_u8_sample: the crop size must be even (W pairs)");
+    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_pack_clip_u8_sample: zero std");
+    REQUIRE(mix_mode >= -1 && mix_mode <= 1, "sf_pack_clip_u8_sample: mix mode must be -1 (none), 0 (mixup) or 1 (cutmix)");
+    if (check_crop_table("sf_pack_clip_u8_sample", crop_host, N, Hs, Ws, S)) return -1;
+    if (mix_mode >= 0 && check_mix_box("sf_pack_clip_u8_sample", mix_mode, S, S, yl, yh, xl, xh)) return -1;
+    REQUIRE((table_host == nullptr) == (table_dev == nullptr), "sf_pack_clip_u8_sample: the erase table needs both of its copies");
+    int64_t most = 0;
+    if (table_host && check_erase_table("sf_pack_clip_u8_sample", table_host, nrows, table_words, erase_mode, N, 3, Tin, S, S, &most))
+        return -1;
+    SamplePackParams m;
+    memset(&m, 0, sizeof(m));
+    PackClipParams& p = m.k;
+    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = Tin; p.Tout = Tout; p.HW = (int64_t)S * S;
+    p.t_index = t_index; p.reverse = reverse; p.out = (f16*)out;
+    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
+    p.total = (int64_t)N * Tout * p.HW;
+    REQUIRE(p.total < (1ll << 31) && (int64_t)N * Tin * Hs * Ws < (1ll << 40), "sf_pack_clip_u8_sample: too many pixels");
+    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)Tout);
+    fill_sample_geom(m.g, crop_dev, Hs, Ws, S);
+    m.mix = mix_mode; m.lam = lam; m.oml = one_minus_lam;
+    if (mix_mode == 1) { m.yl = yl; m.yh = yh; m.xl = xl; m.xh = xh; }
+    m.erase_mode = erase_mode;
+    m.tab = (table_dev && nrows > 0) ? table_dev : nullptr;
+    m.first_row = m.tab ? table_dev + (int64_t)nrows * SF_ERASE_ROW_WORDS : nullptr;
+    hipLaunchKernelGGL(sf_pack_clip_u8_sample_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
+    return check_launch("pack_clip_u8_sample");
 }
 
 static int row_scale_add_impl(const void* x, int32_t ldx, const float* scale, int64_t rows_per_sample, const void* resid,

@@ -28,7 +28,7 @@ def pathway_frame_indices(cfg, num_frames):
                               f"{cfg.MODEL.SINGLE_PATHWAY_ARCH + cfg.MODEL.MULTI_PATHWAY_ARCH}")
 
 
-def pack_pathways_u8(frames, cfg, out=None, mix=None, erase=None):
+def pack_pathways_u8(frames, cfg, out=None, mix=None, erase=None, crop=None):
     """frames: uint8 (N, T, H, W, 3) device tensor (decoded, sampled, cropped).  Returns the model input list: one
     channels-last fp16 tensor per pathway in the W-pair view (N, 8, T', H, W/2), tagged so that the stems use it as is.
     ``out``: tensors of a previous call (e.g. the static input buffers of a captured step.TrainStep) to write into.
@@ -42,7 +42,15 @@ def pack_pathways_u8(frames, cfg, out=None, mix=None, erase=None):
     ``N-1-i`` are each erased with their own rows before they are blended.  Erased values are indexed by the source frame and
     by the channel in DATA.MEAN order, so the Slow pathway stays the ``index_select`` of the Fast one and
     DATA.REVERSE_INPUT_CHANNEL permutes them with the image.  ``erase=None`` (or a table without rows) reaches the kernels
-    above unchanged."""
+    above unchanged.
+    ``crop``: a ``spatial_sampling.CropTable`` (``SpatialSampling.sample_batch(sizes)``): the frames are then the DECODED
+    (N, T, Hs, Ws, 3) buffer, every sample padded to the batch's largest frame, and each sample is resized, cropped and flipped
+    through its own row (csrc/sf_sample.h) to S x S = ``crop.crop_size`` (even) before the erasing and the mixing -- the
+    reference's order (datasets/kinetics.py:402-449).  ``erase`` must then be drawn for the CROPPED clip (T, 3, S, S), the
+    cutmix box of ``mix`` lies in the S x S plane, and the mixing partner is sampled with its own row before the blend.
+    ``crop=None`` reaches the kernels above exactly as before."""
+    if crop is not None:
+        return _pack_pathways_u8_sample(frames, cfg, out, mix, erase, crop)
     assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3 and frames.shape[3] % 2 == 0
     frames = frames.contiguous()
     N, T, H, W, _ = frames.shape
@@ -88,6 +96,52 @@ def pack_pathways_u8(frames, cfg, out=None, mix=None, erase=None):
             get_lib().call("sf_pack_clip_u8", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1], mean[2],
                            std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(),
                            ops._stream(frames), work=dict(bytes=3.0 * N * Tout * H * W + 2.0 * base.numel()))
+        x = base.permute(0, 4, 1, 2, 3)
+        x._sf_wpairs = True                 # already the operand layout of engine.StemConvUnit
+        out.append(x)
+    return out
+
+
+def _pack_pathways_u8_sample(frames, cfg, dst, mix, erase, crop):
+    """pack_pathways_u8 with a crop table: one sf_pack_clip_u8_sample launch per pathway.  Everything is checked before the
+    first launch; a rejected call raises SfError."""
+    from . import random_erasing, spatial_sampling
+    stream = spatial_sampling.check_frames(frames, "pack_pathways_u8")
+    N, T, Hs, Ws, _ = frames.shape
+    S = int(crop.crop_size)
+    if S <= 0 or S % 2:
+        raise _sflib.SfError("pack_pathways_u8: the crop size must be even (got %d)" % S)
+    mean, std = [float(v) for v in cfg.DATA.MEAN], [float(v) for v in cfg.DATA.STD]
+    chost, cdev = spatial_sampling.upload_table(crop, N, frames.device)
+    ehost = edev = None
+    rows = words = emode = 0
+    if erase is not None and len(erase.rows):
+        if tuple(erase.shape) != (T, 3, S, S):
+            raise _sflib.SfError("pack_pathways_u8: the erase table was drawn for (T, C, H, W) = %s, the cropped clip is %s" % (
+                tuple(erase.shape), (T, 3, S, S)))
+        ehost, edev, rows = random_erasing.upload_table(erase, N, frames.device)
+        words, emode = int(ehost.size), random_erasing.MODES[erase.mode]
+    out = []
+    for i, idx in enumerate(pathway_frame_indices(cfg, T)):
+        Tout = T if idx is None else int(idx.numel())
+        idx_dev = None if idx is None else idx.to(device=frames.device, dtype=torch.int32).contiguous()
+        if dst is None:
+            base = torch.empty((N, Tout, S, S // 2, 8), dtype=_f16, device=frames.device)
+        else:
+            base = dst[i].permute(0, 2, 3, 4, 1)
+            if not (tuple(base.shape) == (N, Tout, S, S // 2, 8) and base.is_contiguous() and base.dtype == _f16):
+                raise _sflib.SfError("pack_pathways_u8: out[%d] must be a tensor a previous call returned for the same cropped "
+                                     "clip geometry" % i)
+        mixing = i == 0 and mix is not None and mix.lam != 1.0
+        lam = float(mix.lam) if mixing else 1.0
+        yl, yh, xl, xh = mix.box if mixing and mix.use_cutmix else (0, 0, 0, 0)
+        get_lib().call("sf_pack_clip_u8_sample", frames.data_ptr(), N, T, Hs, Ws, ops._ptr(idx_dev), Tout, mean[0], mean[1],
+                       mean[2], std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(),
+                       chost.ctypes.data, cdev.data_ptr(), S, emode, None if ehost is None else ehost.ctypes.data,
+                       ops._ptr(edev), rows, words, int(bool(mix.use_cutmix)) if mixing else -1, lam, 1.0 - lam, int(yl),
+                       int(yh), int(xl), int(xh), stream,
+                       work=dict(bytes=(24.0 if mixing and not mix.use_cutmix else 12.0) * N * Tout * S * S
+                                 + 2.0 * base.numel()))
         x = base.permute(0, 4, 1, 2, 3)
         x._sf_wpairs = True                 # already the operand layout of engine.StemConvUnit
         out.append(x)

@@ -48,7 +48,8 @@ class PatchEmbed(nn.Module):
         """(B, 3, T, H, W) fp32 clip -> tokens (B, [1 +] T'H'W', C) fp16 (+ the absolute position embedding
         [1, N, C] when given) and the (B, C, T', H', W') shape."""
         out = PatchEmbedFn.apply(x, self, cls_token, pos_embed, self.proj.weight, self.proj.bias)
-        g = self._unit.geom(self._unit.prepare_shape(x.shape))
+        # a clip packed by data.pack_pathways_u8 already has the W-pair shape
+        g = self._unit.geom(x.shape if getattr(x, "_sf_wpairs", False) else self._unit.prepare_shape(x.shape))
         return out, (x.shape[0], self.proj.out_channels, g.To, g.Ho, g.Wo)
 
 
