@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 27
+#define SF_ABI_VERSION 28
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -471,6 +471,31 @@ int sf_pack_clip_u8_sample(const void* frames, int32_t N, int32_t Tin, int32_t H
                            int32_t erase_mode, const int32_t* table_host, const int32_t* table_dev, int32_t nrows,
                            int32_t table_words, int32_t mix_mode, float lam, float one_minus_lam, int32_t yl, int32_t yh,
                            int32_t xl, int32_t xh, sf_stream_t stream);
+/* Colour augmentation of the AVA batch on the device (ABI 28) -- replaces transform.color_jitter, lighting_jitter and
+ * color_normalization and the BGR -> RGB reordering of Ava._images_and_boxes_preprocessing (slowfast/datasets/ava_dataset.py:306-333).
+ * clip is the dense fp32 [N][3][T][HW] clip sf_sample_clip_u8 writes with mean 0 and std 1: the [0, 1] image in the frames' byte
+ * order (BGR for AVA).  The draw arrives as one table of 32-bit words, given twice as the crop table is: table_host is validated
+ * and decides what is launched, table_dev is what the kernels read.  Layout: N rows of 16 words
+ *   op of slot 0, 1, 2 (0 brightness, 1 contrast, 2 saturation, -1 none; no op twice), 0,
+ *   alpha and 1 - alpha of slot 0, 1, 2 (float bits, each the host's double rounded once),
+ *   the addition to input channel 0, 1, 2 (float bits), 0, 0, 0
+ * Per pixel, fp32 without contraction, in slot order: brightness v * a; contrast v * a + m * (1 - a) with m the mean over the
+ * frame of gray = (0.299f * v[2] + 0.587f * v[1]) + 0.114f * v[0] as the values stand at that slot; saturation
+ * v * a + gray(v) * (1 - a); then v + add[c], (v - mean[c]) / std[c], and output channel c = input channel (reverse ? 2 - c : c).
+ * In place.  Kernel launches only, no atomics: two calls give the same bits.
+ *
+ * sf_color_frame_means_f32: means[n * T + t] for the frames of every sample whose row has a contrast slot (the others are left
+ *   untouched; no such row: nothing is launched).  A frame is reduced in sf_color_chunks(HW) chunks of a fixed number of
+ *   pixels; partials needs N * T * sf_color_chunks(HW) floats.  sf_color_sum_depth(): the longest chain of additions a term of a
+ *   frame's sum passes through (what an error bound of the mean is derived from).
+ * sf_color_clip_f32: the streaming pass; means may be NULL when no row has a contrast slot. */
+int sf_color_chunks(int64_t HW);
+int sf_color_sum_depth(void);
+int sf_color_frame_means_f32(const float* clip, int32_t N, int32_t T, int64_t HW, const int32_t* table_host,
+                             const int32_t* table_dev, float* partials, float* means, sf_stream_t stream);
+int sf_color_clip_f32(float* clip, int32_t N, int32_t T, int64_t HW, const int32_t* table_host, const int32_t* table_dev,
+                      const float* means, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                      int32_t reverse, sf_stream_t stream);
 /* Stochastic depth -- replaces drop_path() (slowfast/models/common.py:46-59) at the two residual additions of
  * MultiScaleBlock (attention.py:500-510): y[m] = (resid ? resid[m] : 0) + scale[m / rows_per_sample] * x[m], with
  * scale[b] = floor(keep_prob + u_b) / keep_prob sampled by the caller.  Rows are fp16 [M][C], C % 8 == 0. */

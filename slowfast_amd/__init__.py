@@ -15,4 +15,7 @@ from .mixup import MixUp, construct_mixup  # noqa: F401,E402  (MixUp / CutMix of
 from .random_erasing import RandomErasing, ErasePlan, construct_random_erasing  # noqa: F401,E402  (random erasing on the device)
 from .spatial_sampling import (SpatialSampling, CropRow, CropTable, construct_spatial_sampling,  # noqa: F401,E402
                                sample_clip)  # (scale jitter / crop / flip from uint8 on the device)
+from .spatial_sampling import transform_boxes, collate_boxes, construct_ava_sampling  # noqa: F401,E402  (AVA: boxes follow the crop)
+from .color_augmentation import (ColorAugmentation, ColorRow, ColorTable, construct_color_augmentation,  # noqa: F401,E402
+                                 color_clip)  # (colour jitter / PCA lighting / normalisation of the AVA clip on the device)
 from .losses import get_loss_func  # noqa: F401,E402

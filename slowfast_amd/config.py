@@ -97,11 +97,17 @@ _DEFAULTS = {
              "REVERSE_INPUT_CHANNEL": False,
              # slowfast/config/defaults.py:696-737 (the keys spatial_sampling.construct_spatial_sampling reads)
              "TRAIN_JITTER_SCALES": [256, 320], "TRAIN_JITTER_SCALES_RELATIVE": [], "TRAIN_JITTER_ASPECT_RELATIVE": [],
-             "TRAIN_JITTER_MOTION_SHIFT": False, "INV_UNIFORM_SAMPLE": False, "RANDOM_FLIP": True},
+             "TRAIN_JITTER_MOTION_SHIFT": False, "INV_UNIFORM_SAMPLE": False, "RANDOM_FLIP": True,
+             # slowfast/config/defaults.py:672-679 (PCA lighting jitter, color_augmentation.construct_color_augmentation)
+             "TRAIN_PCA_EIGVAL": [0.225, 0.224, 0.229],
+             "TRAIN_PCA_EIGVEC": [[-0.5675, 0.7192, 0.4009], [-0.5808, -0.0045, -0.8140], [-0.5836, -0.6948, 0.4203]]},
     "SOLVER": {"BASE_LR": 0.1, "MOMENTUM": 0.9, "DAMPENING": 0.0, "NESTEROV": True, "WEIGHT_DECAY": 1e-4,
                "OPTIMIZING_METHOD": "sgd", "ZERO_WD_1D_PARAM": False, "CLIP_GRAD_VAL": None,
                "CLIP_GRAD_L2NORM": None, "LAYER_DECAY": 1.0},
     "DETECTION": {"ENABLE": False, "ALIGNED": True, "SPATIAL_SCALE_FACTOR": 16, "ROI_XFORM_RESOLUTION": 7},
+    # slowfast/config/defaults.py:999-1010 (the keys the AVA clip preprocessing reads; IMG_PROC_BACKEND is not one of them:
+    # the arithmetic is the pytorch backend's)
+    "AVA": {"BGR": False, "TRAIN_USE_COLOR_AUGMENTATION": False, "TRAIN_PCA_JITTER_ONLY": True, "TEST_FORCE_FLIP": False},
     "MULTIGRID": {"SHORT_CYCLE": False, "LONG_CYCLE": False},
     "CONTRASTIVE": {"NUM_MLP_LAYERS": 1, "MLP_DIM": 2048, "BN_MLP": False, "BN_SYNC_MLP": False,
                     "PREDICTOR_DEPTHS": []},

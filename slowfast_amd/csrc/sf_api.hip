@@ -18,6 +18,7 @@
 #include "sf_mixup.h"
 #include "sf_erase.h"
 #include "sf_sample.h"
+#include "sf_color.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2748,6 +2749,88 @@ extern "C" int sf_pack_clip_u8_sample(const void* frames, int32_t N, int32_t Tin
     m.first_row = m.tab ? table_dev + (int64_t)nrows * SF_ERASE_ROW_WORDS : nullptr;
     hipLaunchKernelGGL(sf_pack_clip_u8_sample_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
     return check_launch("pack_clip_u8_sample");
+}
+
+// ================================================================================================
+// Colour augmentation of the AVA batch (sf_color.h; replaces transform.color_jitter / lighting_jitter / color_normalization and
+// the channel reordering on the host clip, datasets/ava_dataset.py:306-333).  The draw arrives as one table with a row per sample
+// (layout: sf_color.h); the HOST copy is validated and decides what is launched, the kernels read the device copy.  Kernel
+// launches only.
+extern "C" int sf_color_chunks(int64_t HW) {
+    REQUIRE(HW > 0 && HW <= (int64_t)SF_COLOR_CHUNK * SF_COLOR_MAX_CHUNKS, "sf_color_chunks: a frame must have 1 .. %d pixels",
+            SF_COLOR_CHUNK * SF_COLOR_MAX_CHUNKS);
+    return (int)((HW + SF_COLOR_CHUNK - 1) / SF_COLOR_CHUNK);
+}
+extern "C" int sf_color_sum_depth(void) { return SF_COLOR_SUM_DEPTH; }
+// returns the number of rows with a contrast slot, -1 for a bad table
+static int check_color_table(const char* who, const int32_t* th, int32_t N) {
+    REQUIRE(th, "%s: null colour table", who);
+    int contrast = 0;
+    for (int n = 0; n < N; ++n) {
+        const int32_t* w = th + (int64_t)n * SF_COLOR_ROW_WORDS;
+        int seen = 0;
+        for (int s = 0; s < 3; ++s) {
+            REQUIRE(w[s] >= -1 && w[s] <= 2, "%s: colour row %d: op %d of slot %d is none of -1, 0, 1, 2", who, n, w[s], s);
+            if (w[s] < 0) continue;
+            REQUIRE(!(seen >> w[s] & 1), "%s: colour row %d: op %d appears twice", who, n, w[s]);
+            seen |= 1 << w[s];
+        }
+        for (int k = 4; k < 13; ++k)                        // an exponent of all ones: infinity or NaN
+            REQUIRE((w[k] & 0x7f800000) != 0x7f800000, "%s: colour row %d: word %d is not a finite float", who, n, k);
+        contrast += seen >> 1 & 1;
+    }
+    return contrast;
+}
+static int fill_color_params(const char* who, ColorParams& p, const float* clip, int32_t N, int32_t T, int64_t HW,
+                             const int32_t* table_dev, bool& vec) {
+    REQUIRE(clip && table_dev, "%s: null pointer", who);
+    REQUIRE(N > 0 && T > 0 && (int64_t)N * T <= 65535, "%s: bad shape (N * T must be 1 .. 65535)", who);
+    REQUIRE(HW > 0 && HW <= (int64_t)SF_COLOR_CHUNK * SF_COLOR_MAX_CHUNKS, "%s: a frame must have 1 .. %d pixels", who,
+            SF_COLOR_CHUNK * SF_COLOR_MAX_CHUNKS);
+    REQUIRE((int64_t)N * T * HW < (1ll << 31), "%s: too many pixels", who);
+    REQUIRE((uintptr_t)clip % 4 == 0, "%s: the clip must be 4-byte aligned", who);
+    memset(&p, 0, sizeof(p));
+    p.clip = const_cast<float*>(clip); p.table = table_dev; p.N = N; p.T = T; p.HW = HW;
+    p.chunks = (int)((HW + SF_COLOR_CHUNK - 1) / SF_COLOR_CHUNK);
+    vec = (uintptr_t)clip % 16 == 0 && HW % 4 == 0;         // every (n, c, t) plane then starts on a 16-byte boundary
+    return 0;
+}
+extern "C" int sf_color_frame_means_f32(const float* clip, int32_t N, int32_t T, int64_t HW, const int32_t* table_host,
+                                        const int32_t* table_dev, float* partials, float* means, sf_stream_t stream) {
+    ColorParams p;
+    bool vec;
+    if (fill_color_params("sf_color_frame_means_f32", p, clip, N, T, HW, table_dev, vec)) return -1;
+    REQUIRE(partials && means, "sf_color_frame_means_f32: null pointer");
+    const int contrast = check_color_table("sf_color_frame_means_f32", table_host, N);
+    if (contrast < 0) return -1;
+    if (contrast == 0) return 0;                            // nothing to reduce: nothing is launched
+    p.partials = partials; p.means = means;
+    const dim3 grid(p.chunks, N * T);
+    if (vec) hipLaunchKernelGGL(sf_color_frame_sums_kernel<4>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(sf_color_frame_sums_kernel<1>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    if (check_launch("color_frame_sums")) return -1;
+    hipLaunchKernelGGL(sf_color_frame_means_kernel, dim3(cdiv(N * T, SF_THREADS)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("color_frame_means");
+}
+extern "C" int sf_color_clip_f32(float* clip, int32_t N, int32_t T, int64_t HW, const int32_t* table_host,
+                                 const int32_t* table_dev, const float* means, float mean0, float mean1, float mean2, float std0,
+                                 float std1, float std2, int32_t reverse, sf_stream_t stream) {
+    ColorParams p;
+    bool vec;
+    if (fill_color_params("sf_color_clip_f32", p, clip, N, T, HW, table_dev, vec)) return -1;
+    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_color_clip_f32: zero std");
+    const int contrast = check_color_table("sf_color_clip_f32", table_host, N);
+    if (contrast < 0) return -1;
+    REQUIRE(contrast == 0 || means, "sf_color_clip_f32: a row with contrast needs the frame means");
+    p.means = const_cast<float*>(means);
+    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
+    p.reverse = reverse;
+    const int V = vec ? 4 : 1;
+    p.total = (int64_t)N * T * (HW / V);
+    p.fdG = make_fastdiv((uint32_t)(HW / V)); p.fdT = make_fastdiv((uint32_t)T);
+    if (vec) hipLaunchKernelGGL(sf_color_clip_kernel<4>, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(sf_color_clip_kernel<1>, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("color_clip_f32");
 }
 
 static int row_scale_add_impl(const void* x, int32_t ldx, const float* scale, int64_t rows_per_sample, const void* resid,

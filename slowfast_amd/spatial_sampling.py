@@ -101,7 +101,7 @@ class SpatialSampling:
     """The arguments of slowfast/datasets/utils.py:spatial_sampling without ``frames``."""
 
     def __init__(self, spatial_idx=-1, min_scale=256, max_scale=320, crop_size=224, random_horizontal_flip=True,
-                 inverse_uniform_sampling=False, aspect_ratio=None, scale=None, motion_shift=False):
+                 inverse_uniform_sampling=False, aspect_ratio=None, scale=None, motion_shift=False, force_flip=False):
         if motion_shift:
             raise NotImplementedError("SpatialSampling: motion_shift (per-frame boxes) is not supported")
         if spatial_idx not in (-1, 0, 1, 2):
@@ -119,6 +119,9 @@ class SpatialSampling:
         self.aspect_ratio = None if aspect_ratio is None else tuple(aspect_ratio)
         self.scale = None if scale is None else tuple(scale)
         self.motion_shift = False
+        # AVA.TEST_FORCE_FLIP (construct_ava_sampling): every row of the test path flips.  The reference's
+        # horizontal_flip(1, ...) still compares one np.random.uniform() with 1, so one is consumed here too.
+        self.force_flip = bool(force_flip)
 
     # ---- the draw (host) ------------------------------------------------------------------------------------------
     @staticmethod
@@ -188,6 +191,9 @@ class SpatialSampling:
             else:
                 ox = 0 if idx == 0 else (rw - S if idx == 2 else ox)
             flip = 0
+            if self.force_flip:
+                np.random.uniform()
+                flip = 1
         return CropRow(height, width, 0, 0, height, width, rh, rw, oy, ox, flip)
 
     def _check(self, height, width, idx):
@@ -269,3 +275,71 @@ def construct_spatial_sampling(cfg, mode):
         aspect_ratio=None if (mode != "train" or len(asp) == 0) else asp,
         scale=None if (mode != "train" or len(scl) == 0) else scl,
         motion_shift=cfg.DATA.TRAIN_JITTER_MOTION_SHIFT if mode == "train" else False)
+
+
+# ---- AVA: the boxes follow the crop ---------------------------------------------------------------------------------------
+def _clip_boxes(boxes, height, width):
+    out = boxes.copy()
+    out[:, [0, 2]] = np.minimum(width - 1.0, np.maximum(0.0, boxes[:, [0, 2]]))
+    out[:, [1, 3]] = np.minimum(height - 1.0, np.maximum(0.0, boxes[:, [1, 3]]))
+    return out
+
+
+def transform_boxes(row, boxes, crop_size):
+    """The boxes of a clip carried through its ``CropRow`` as Ava._images_and_boxes_preprocessing carries them
+    (datasets/ava_dataset.py:255-302, :335): ``boxes`` is a (K, 4) array of [x1, y1, x2, y2] in [0, 1]; they are scaled to the
+    source frame and clipped to it, scaled with the short-side resize (skipped when the row resizes nothing), moved by the
+    crop offset, mirrored when the row flips and clipped to the crop.  numpy, in the reference's operations and order: float64
+    boxes come out bit for bit.  The input is not modified."""
+    r = CropRow(*[int(v) for v in row])
+    S = int(crop_size)
+    if (r.win_y, r.win_x, r.win_h, r.win_w) != (0, 0, r.src_h, r.src_w):
+        raise SfError("transform_boxes: the row must resize the whole frame (the jitter and test paths), not a window of it")
+    boxes = np.array(boxes, copy=True)
+    if boxes.ndim != 2 or boxes.shape[1] != 4 or not np.issubdtype(boxes.dtype, np.floating):
+        raise SfError("transform_boxes: boxes must be a floating (K, 4) array of [x1, y1, x2, y2]")
+    boxes[:, [0, 2]] *= r.src_w
+    boxes[:, [1, 3]] *= r.src_h
+    boxes = _clip_boxes(boxes, r.src_h, r.src_w)
+    if (r.res_h, r.res_w) != (r.src_h, r.src_w):
+        if r.src_w < r.src_h:
+            boxes = boxes * float(r.res_h) / r.src_h
+        else:
+            boxes = boxes * float(r.res_w) / r.src_w
+    moved = boxes.copy()
+    moved[:, [0, 2]] = boxes[:, [0, 2]] - r.off_x
+    moved[:, [1, 3]] = boxes[:, [1, 3]] - r.off_y
+    boxes = moved
+    if r.flip:
+        flipped = boxes.copy()
+        flipped[:, [0, 2]] = S - boxes[:, [2, 0]] - 1
+        boxes = flipped
+    return _clip_boxes(boxes, S, S)
+
+
+def collate_boxes(list_of_boxes):
+    """The (R, 5) float32 tensor [batch index, x1, y1, x2, y2] that loader.detection_collate builds from every sample's (K_n, 4)
+    boxes: the ``bboxes`` input of ResNetRoIHead.  A sample without boxes contributes no row."""
+    rows = []
+    for n, boxes in enumerate(list_of_boxes):
+        boxes = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+        rows.append(np.concatenate([np.full((boxes.shape[0], 1), float(n)), boxes], axis=1))
+    out = np.concatenate(rows, axis=0) if rows else np.zeros((0, 5))
+    return torch.tensor(out).float()
+
+
+def construct_ava_sampling(cfg, split):
+    """The crop arguments of Ava.__init__ / Ava._images_and_boxes_preprocessing (datasets/ava_dataset.py:37-48, :262-290):
+    "train" jitters at DATA.TRAIN_JITTER_SCALES, crops TRAIN_CROP_SIZE at random and draws the flip; "val" resizes the short
+    side to TEST_CROP_SIZE and takes the centre crop, with AVA.TEST_FORCE_FLIP every row flips (the reference's
+    horizontal_flip(1, ...) consumes one np.random.uniform() whose value cannot matter; so does the draw here).
+    "test" is not cropped by the reference (the clip is not square) and is not supported; neither is
+    DATA.TRAIN_JITTER_MOTION_SHIFT."""
+    if split == "train":
+        return SpatialSampling(spatial_idx=-1, min_scale=cfg.DATA.TRAIN_JITTER_SCALES[0], max_scale=cfg.DATA.TRAIN_JITTER_SCALES[1],
+                               crop_size=cfg.DATA.TRAIN_CROP_SIZE, random_horizontal_flip=True)
+    if split == "val":
+        S = cfg.DATA.TEST_CROP_SIZE
+        return SpatialSampling(spatial_idx=1, min_scale=S, max_scale=S, crop_size=S, random_horizontal_flip=False,
+                               force_flip=bool(cfg.AVA.TEST_FORCE_FLIP))
+    raise NotImplementedError("construct_ava_sampling: the {} split is not supported".format(split))
