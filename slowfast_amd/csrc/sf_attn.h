@@ -510,7 +510,8 @@ __global__ __launch_bounds__(SF_THREADS, QT == 2 ? 2 : 3) void sf_attn_bwd_dq_ke
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                // keys beyond Nk: K, V rows are zero -> x = 0, dp = 0; their p must not reach dq / drq
+                // keys beyond Nk: KeyChunkCopy filled their K, V rows with copies of row Nk - 1, so x and dp are that key's
+                // (finite, not zero); their p must not reach dq / drq
                 const bool kin = c * 32 + 16 * t + 4 * g + r < p.Nk;
 #pragma unroll
                 for (int u = 0; u < QT; ++u) {
