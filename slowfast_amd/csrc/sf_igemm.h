@@ -24,7 +24,10 @@ struct IgemmParams {
     const float* bias;  // optional [Nout]
     const f16* resid;   // optional [M][ldr] added in the epilogue (dgrad accumulation)
     int ldr;
-    float* stat_part;   // optional [mtiles][2][Nout] per-tile column sum / sum of squares (BatchNorm)
+    float* stat_part;   // optional [mtiles][2][Nout] per-tile column sum / sum of squares (BatchNorm).  Summed from the fp32
+                        // accumulators (bias included), i.e. BEFORE the rounding to the storage type that the BatchNorm later
+                        // reads: the statistics describe the unrounded convolution (parity method; bnb_part below is
+                        // the opposite: sums of the STORED values)
     int ntiles_n;
     // batched GEMMs (attention): blockIdx.y = b*bh + j, operands advance by (b, j) strides (elements)
     int bh;

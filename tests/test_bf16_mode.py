@@ -47,7 +47,8 @@ def test_bf16_builds_identify_themselves():
 def test_bf16_kernels_and_blocks_hostsim():
     """Kernel, token-kernel, implicit-GEMM-variant and block-level checks on the host simulator's bf16 build."""
     _run_pytest_bf16(["tests/test_kernels_hostsim.py", "tests/test_x3d_kernels_hostsim.py", "tests/test_tokens_hostsim.py",
-                      "tests/test_token_elem_hostsim.py", "tests/test_igemm2_hostsim.py", "tests/test_blocks_hostsim.py", "-m", "not gpu"], timeout=1500)
+                      "tests/test_token_elem_hostsim.py", "tests/test_igemm2_hostsim.py", "tests/test_conv_elem_hostsim.py", "tests/test_blocks_hostsim.py", "-m", "not gpu"],
+                     timeout=1500)
 
 
 def test_bf16_models_hostsim():
@@ -62,7 +63,8 @@ def test_bf16_kernels_on_gpu():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    print(_run_pytest_bf16(["tests/test_kernels_gpu.py", "tests/test_tokens_gpu.py", "tests/test_token_elem_gpu.py", "-m", "gpu"], timeout=1500)[-300:])
+    print(_run_pytest_bf16(["tests/test_kernels_gpu.py", "tests/test_tokens_gpu.py", "tests/test_token_elem_gpu.py",
+                            "tests/test_conv_elem_gpu.py", "-m", "gpu"], timeout=1500)[-300:])
 
 
 @pytest.mark.gpu
