@@ -17,6 +17,7 @@
 #include "sf_optim.h"
 #include "sf_mixup.h"
 #include "sf_erase.h"
+#include "sf_pack.h"
 #include "sf_sample.h"
 #include "sf_color.h"
 
@@ -2463,24 +2464,6 @@ extern "C" int sf_roi_align_max_bwd(int32_t R, int32_t B, int32_t H, int32_t W, 
     return check_launch("roi_align_max_bwd");
 }
 
-extern "C" int sf_pack_clip_u8(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
-                               int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
-                               int32_t reverse, void* out, sf_stream_t stream) {
-    REQUIRE(frames && out, "sf_pack_clip_u8: null pointer");
-    REQUIRE(N > 0 && Tin > 0 && Tout > 0 && H > 0 && W > 0 && W % 2 == 0, "sf_pack_clip_u8: bad shape (W must be even)");
-    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_pack_clip_u8: zero std");
-    PackClipParams p;
-    memset(&p, 0, sizeof(p));
-    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = Tin; p.Tout = Tout; p.HW = (int64_t)H * W;
-    p.t_index = t_index; p.reverse = reverse; p.out = (f16*)out;
-    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
-    p.total = (int64_t)N * Tout * p.HW;
-    REQUIRE(p.total < (1ll << 31) && (int64_t)N * Tin * p.HW < (1ll << 40), "sf_pack_clip_u8: too many pixels");
-    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)Tout);
-    hipLaunchKernelGGL(sf_pack_clip_u8_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
-    return check_launch("pack_clip_u8");
-}
-
 // ================================================================================================
 // MixUp / CutMix of the batch (sf_mixup.h; replaces mixup_fn(inputs[0], labels), tools/train_net.py:109-111).  Kernel
 // launches only, scalars by value: they run eagerly between two replays and write the step's static buffers.
@@ -2539,28 +2522,6 @@ extern "C" int sf_mix_clip_f32(const float* src, float* dst, int32_t B, int32_t 
     p.items = planes * H * ngroups;
     hipLaunchKernelGGL(sf_cutmix_copy_kernel, dim3(mix_grid_x(p.items, B), B), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("mix_clip_f32 (cutmix copy)");
-}
-extern "C" int sf_pack_clip_u8_mix(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
-                                   int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
-                                   int32_t reverse, void* out, int32_t mode, float lam, float one_minus_lam, int32_t yl,
-                                   int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream) {
-    REQUIRE(frames && out, "sf_pack_clip_u8_mix: null pointer");
-    REQUIRE(N > 0 && Tin > 0 && Tout > 0 && H > 0 && W > 0 && W % 2 == 0, "sf_pack_clip_u8_mix: bad shape (W must be even)");
-    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_pack_clip_u8_mix: zero std");
-    if (check_mix_box("sf_pack_clip_u8_mix", mode, H, W, yl, yh, xl, xh)) return -1;
-    PackClipMixParams m;
-    memset(&m, 0, sizeof(m));
-    PackClipParams& p = m.k;
-    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = Tin; p.Tout = Tout; p.HW = (int64_t)H * W;
-    p.t_index = t_index; p.reverse = reverse; p.out = (f16*)out;
-    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
-    p.total = (int64_t)N * Tout * p.HW;
-    REQUIRE(p.total < (1ll << 31) && (int64_t)N * Tin * p.HW < (1ll << 40), "sf_pack_clip_u8_mix: too many pixels");
-    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)Tout);
-    m.W = W; m.mode = mode; m.lam = lam; m.oml = one_minus_lam; m.yl = yl; m.yh = yh; m.xl = xl; m.xh = xh;
-    m.fdW = make_fastdiv((uint32_t)W);
-    hipLaunchKernelGGL(sf_pack_clip_u8_mix_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
-    return check_launch("pack_clip_u8_mix");
 }
 extern "C" int sf_mix_targets(const int64_t* labels, int32_t B, int32_t K, float on_value, float off_value, float lam,
                               float one_minus_lam, float* out, sf_stream_t stream) {
@@ -2634,39 +2595,6 @@ extern "C" int sf_erase_clip_f32(const float* src, float* dst, int32_t N, int32_
     hipLaunchKernelGGL(sf_erase_copy_kernel, dim3(mix_grid_x(p.items, N), N), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("erase_clip_f32 (copy)");
 }
-extern "C" int sf_pack_clip_u8_aug(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
-                                   int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
-                                   int32_t reverse, void* out, int32_t erase_mode, const int32_t* table_host,
-                                   const int32_t* table_dev, int32_t nrows, int32_t table_words, int32_t mix_mode, float lam,
-                                   float one_minus_lam, int32_t yl, int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream) {
-    REQUIRE(frames && out, "sf_pack_clip_u8_aug: null pointer");
-    REQUIRE(N > 0 && Tin > 0 && Tout > 0 && H > 0 && W > 0 && W % 2 == 0, "sf_pack_clip_u8_aug: bad shape (W must be even)");
-    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_pack_clip_u8_aug: zero std");
-    REQUIRE(mix_mode >= -1 && mix_mode <= 1, "sf_pack_clip_u8_aug: mix mode must be -1 (none), 0 (mixup) or 1 (cutmix)");
-    if (mix_mode >= 0 && check_mix_box("sf_pack_clip_u8_aug", mix_mode, H, W, yl, yh, xl, xh)) return -1;
-    REQUIRE((table_host == nullptr) == (table_dev == nullptr), "sf_pack_clip_u8_aug: the erase table needs both of its copies");
-    int64_t most = 0;
-    if (table_host && check_erase_table("sf_pack_clip_u8_aug", table_host, nrows, table_words, erase_mode, N, 3, Tin, H, W, &most))
-        return -1;
-    PackClipAugParams m;
-    memset(&m, 0, sizeof(m));
-    PackClipParams& p = m.k;
-    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = Tin; p.Tout = Tout; p.HW = (int64_t)H * W;
-    p.t_index = t_index; p.reverse = reverse; p.out = (f16*)out;
-    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
-    p.total = (int64_t)N * Tout * p.HW;
-    REQUIRE(p.total < (1ll << 31) && (int64_t)N * Tin * p.HW < (1ll << 40), "sf_pack_clip_u8_aug: too many pixels");
-    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)Tout);
-    m.H = H; m.W = W; m.mix = mix_mode; m.lam = lam; m.oml = one_minus_lam;
-    if (mix_mode == 1) { m.yl = yl; m.yh = yh; m.xl = xl; m.xh = xh; }
-    m.erase_mode = erase_mode;
-    m.tab = (table_dev && nrows > 0) ? table_dev : nullptr;
-    m.first_row = m.tab ? table_dev + (int64_t)nrows * SF_ERASE_ROW_WORDS : nullptr;
-    m.fdW = make_fastdiv((uint32_t)W);
-    hipLaunchKernelGGL(sf_pack_clip_u8_aug_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
-    return check_launch("pack_clip_u8_aug");
-}
-
 // ================================================================================================
 // Spatial sampling of the batch (sf_sample.h; replaces utils.spatial_sampling on the normalised host clip,
 // datasets/kinetics.py:410-435).  The draw arrives as one table with a row per sample (layout: sf_sample.h); the HOST copy is
@@ -2691,8 +2619,18 @@ static int check_crop_table(const char* who, const int32_t* th, int32_t N, int32
     }
     return 0;
 }
+// what every kernel that reads uint8 frames through pack_clip_norm needs: the source, the (n, t, row, column) index space of
+// Ho x Wo output planes and the normalisation
+static void fill_pack_clip(PackClipParams& p, const void* frames, int32_t N, int32_t Tin, int32_t Tout, int32_t Ho, int32_t Wo,
+                           float mean0, float mean1, float mean2, float std0, float std1, float std2) {
+    const int64_t HW = (int64_t)Ho * Wo;
+    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = Tin; p.Tout = Tout; p.HW = HW;
+    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
+    p.total = (int64_t)N * Tout * HW;
+    p.fdHW = make_fastdiv((uint32_t)HW); p.fdT = make_fastdiv((uint32_t)Tout); p.fdW = make_fastdiv((uint32_t)Wo);
+}
 static void fill_sample_geom(SampleGeom& g, const int32_t* crop_dev, int32_t Hs, int32_t Ws, int32_t S) {
-    g.crop = crop_dev; g.Hs = Hs; g.Ws = Ws; g.S = S; g.fdS = make_fastdiv((uint32_t)S);
+    g.crop = crop_dev; g.Hs = Hs; g.Ws = Ws; g.S = S;
 }
 extern "C" int sf_sample_clip_u8(const void* frames, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* crop_host,
                                  const int32_t* crop_dev, int32_t S, float mean0, float mean1, float mean2, float std0,
@@ -2705,15 +2643,89 @@ extern "C" int sf_sample_clip_u8(const void* frames, int32_t N, int32_t T, int32
     SampleClipParams m;
     memset(&m, 0, sizeof(m));
     PackClipParams& p = m.k;
-    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = T; p.Tout = T; p.HW = (int64_t)S * S;
-    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
-    p.total = (int64_t)N * T * p.HW;
+    fill_pack_clip(p, frames, N, T, T, S, S, mean0, mean1, mean2, std0, std1, std2);
     REQUIRE(p.total < (1ll << 31) && (int64_t)N * T * Hs * Ws < (1ll << 40), "sf_sample_clip_u8: too many pixels");
-    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)T);
-    fill_sample_geom(m.g, crop_dev, Hs, Ws, S);
+    fill_sample_geom(p.g, crop_dev, Hs, Ws, S);
     m.dst = out;
     hipLaunchKernelGGL(sf_sample_clip_u8_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
     return check_launch("sample_clip_u8");
+}
+
+// ================================================================================================
+// The packed path (sf_pack.h): decoded uint8 frames -> the stems' W-pair buffer, one launch per pathway, with the batch's input
+// stages between the pixel and the rounding.  One launcher behind the four entry points; what an entry point's argument list
+// does not carry arrives as a null stage.  Kernel launches only.
+struct PackCrop { const int32_t* host; const int32_t* dev; int32_t S; };
+struct PackErase { int32_t mode; const int32_t* host; const int32_t* dev; int32_t nrows, words; };
+struct PackMix { int32_t mode; float lam, oml; int32_t yl, yh, xl, xh; };
+// H x W: the frames (with a crop: the padded source buffer, and the output plane is S x S).  The entry points with an erase
+// stage take mix mode -1 (no mixing); sf_pack_clip_u8_mix always mixes.
+static int pack_clip_impl(const char* who, const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
+                          int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2, int32_t reverse,
+                          void* out, const PackCrop* crop, const PackErase* erase, const PackMix* mix, sf_stream_t stream) {
+    REQUIRE(frames && out && (!crop || crop->dev), "%s: null pointer", who);
+    if (crop) {
+        REQUIRE(N > 0 && Tin > 0 && Tout > 0, "%s: bad shape", who);
+        REQUIRE(crop->S > 0 && crop->S % 2 == 0, "%s: the crop size must be even (W pairs)", who);
+    } else {
+        REQUIRE(N > 0 && Tin > 0 && Tout > 0 && H > 0 && W > 0 && W % 2 == 0, "%s: bad shape (W must be even)", who);
+    }
+    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "%s: zero std", who);
+    const int32_t Ho = crop ? crop->S : H, Wo = crop ? crop->S : W;     // the output plane: erase table and cutmix box live in it
+    const bool mixing = mix && !(erase && mix->mode == -1);
+    if (mix && erase) REQUIRE(mix->mode >= -1 && mix->mode <= 1, "%s: mix mode must be -1 (none), 0 (mixup) or 1 (cutmix)", who);
+    if (crop && check_crop_table(who, crop->host, N, H, W, crop->S)) return -1;
+    if (mixing && check_mix_box(who, mix->mode, Ho, Wo, mix->yl, mix->yh, mix->xl, mix->xh)) return -1;
+    int64_t most = 0;
+    if (erase) {
+        REQUIRE((erase->host == nullptr) == (erase->dev == nullptr), "%s: the erase table needs both of its copies", who);
+        if (erase->host && check_erase_table(who, erase->host, erase->nrows, erase->words, erase->mode, N, 3, Tin, Ho, Wo, &most))
+            return -1;
+    }
+    PackClipParams p;
+    memset(&p, 0, sizeof(p));
+    fill_pack_clip(p, frames, N, Tin, Tout, Ho, Wo, mean0, mean1, mean2, std0, std1, std2);
+    REQUIRE(p.total < (1ll << 31) && (int64_t)N * Tin * H * W < (1ll << 40), "%s: too many pixels", who);
+    p.t_index = t_index; p.reverse = reverse; p.out = (f16*)out;
+    p.mix = mixing ? mix->mode : -1;
+    if (mixing) { p.lam = mix->lam; p.oml = mix->oml; }
+    if (p.mix == 1) { p.yl = mix->yl; p.yh = mix->yh; p.xl = mix->xl; p.xh = mix->xh; }
+    if (erase && erase->dev && erase->nrows > 0) {
+        p.erase_mode = erase->mode;
+        p.tab = erase->dev;
+        p.first_row = erase->dev + (int64_t)erase->nrows * SF_ERASE_ROW_WORDS;
+    }
+    if (crop) fill_sample_geom(p.g, crop->dev, H, W, crop->S);
+    const dim3 grid(pool_grid(p.total)), block(SF_THREADS);
+    if (crop) hipLaunchKernelGGL((sf_pack_clip_kernel<PackSampled, true, true>), grid, block, 0, (hipStream_t)stream, p);
+    else if (erase) hipLaunchKernelGGL((sf_pack_clip_kernel<PackDirect, true, true>), grid, block, 0, (hipStream_t)stream, p);
+    else if (mix) hipLaunchKernelGGL((sf_pack_clip_kernel<PackDirect, false, true>), grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((sf_pack_clip_kernel<PackDirect, false, false>), grid, block, 0, (hipStream_t)stream, p);
+    return check_launch(who + 3);           // "pack_clip_u8..."
+}
+extern "C" int sf_pack_clip_u8(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
+                               int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                               int32_t reverse, void* out, sf_stream_t stream) {
+    return pack_clip_impl("sf_pack_clip_u8", frames, N, Tin, H, W, t_index, Tout, mean0, mean1, mean2, std0, std1, std2, reverse, out,
+                          nullptr, nullptr, nullptr, stream);
+}
+extern "C" int sf_pack_clip_u8_mix(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
+                                   int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                                   int32_t reverse, void* out, int32_t mode, float lam, float one_minus_lam, int32_t yl,
+                                   int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream) {
+    const PackMix mix = {mode, lam, one_minus_lam, yl, yh, xl, xh};
+    return pack_clip_impl("sf_pack_clip_u8_mix", frames, N, Tin, H, W, t_index, Tout, mean0, mean1, mean2, std0, std1, std2, reverse,
+                          out, nullptr, nullptr, &mix, stream);
+}
+extern "C" int sf_pack_clip_u8_aug(const void* frames, int32_t N, int32_t Tin, int32_t H, int32_t W, const int32_t* t_index,
+                                   int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                                   int32_t reverse, void* out, int32_t erase_mode, const int32_t* table_host,
+                                   const int32_t* table_dev, int32_t nrows, int32_t table_words, int32_t mix_mode, float lam,
+                                   float one_minus_lam, int32_t yl, int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream) {
+    const PackErase erase = {erase_mode, table_host, table_dev, nrows, table_words};
+    const PackMix mix = {mix_mode, lam, one_minus_lam, yl, yh, xl, xh};
+    return pack_clip_impl("sf_pack_clip_u8_aug", frames, N, Tin, H, W, t_index, Tout, mean0, mean1, mean2, std0, std1, std2, reverse,
+                          out, nullptr, &erase, &mix, stream);
 }
 extern "C" int sf_pack_clip_u8_sample(const void* frames, int32_t N, int32_t Tin, int32_t Hs, int32_t Ws, const int32_t* t_index,
                                       int32_t Tout, float mean0, float mean1, float mean2, float std0, float std1, float std2,
@@ -2721,34 +2733,11 @@ extern "C" int sf_pack_clip_u8_sample(const void* frames, int32_t N, int32_t Tin
                                       int32_t erase_mode, const int32_t* table_host, const int32_t* table_dev, int32_t nrows,
                                       int32_t table_words, int32_t mix_mode, float lam, float one_minus_lam, int32_t yl,
                                       int32_t yh, int32_t xl, int32_t xh, sf_stream_t stream) {
-    REQUIRE(frames && out && crop_dev, "sf_pack_clip_u8_sample: null pointer");
-    REQUIRE(N > 0 && Tin > 0 && Tout > 0, "sf_pack_clip_u8_sample: bad shape");
-    REQUIRE(S > 0 && S % 2 == 0, "sf_pack_clip_u8_sample: the crop size must be even (W pairs)");
-    REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "sf_pack_clip_u8_sample: zero std");
-    REQUIRE(mix_mode >= -1 && mix_mode <= 1, "sf_pack_clip_u8_sample: mix mode must be -1 (none), 0 (mixup) or 1 (cutmix)");
-    if (check_crop_table("sf_pack_clip_u8_sample", crop_host, N, Hs, Ws, S)) return -1;
-    if (mix_mode >= 0 && check_mix_box("sf_pack_clip_u8_sample", mix_mode, S, S, yl, yh, xl, xh)) return -1;
-    REQUIRE((table_host == nullptr) == (table_dev == nullptr), "sf_pack_clip_u8_sample: the erase table needs both of its copies");
-    int64_t most = 0;
-    if (table_host && check_erase_table("sf_pack_clip_u8_sample", table_host, nrows, table_words, erase_mode, N, 3, Tin, S, S, &most))
-        return -1;
-    SamplePackParams m;
-    memset(&m, 0, sizeof(m));
-    PackClipParams& p = m.k;
-    p.frames = (const unsigned char*)frames; p.N = N; p.Tin = Tin; p.Tout = Tout; p.HW = (int64_t)S * S;
-    p.t_index = t_index; p.reverse = reverse; p.out = (f16*)out;
-    p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2; p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
-    p.total = (int64_t)N * Tout * p.HW;
-    REQUIRE(p.total < (1ll << 31) && (int64_t)N * Tin * Hs * Ws < (1ll << 40), "sf_pack_clip_u8_sample: too many pixels");
-    p.fdHW = make_fastdiv((uint32_t)p.HW); p.fdT = make_fastdiv((uint32_t)Tout);
-    fill_sample_geom(m.g, crop_dev, Hs, Ws, S);
-    m.mix = mix_mode; m.lam = lam; m.oml = one_minus_lam;
-    if (mix_mode == 1) { m.yl = yl; m.yh = yh; m.xl = xl; m.xh = xh; }
-    m.erase_mode = erase_mode;
-    m.tab = (table_dev && nrows > 0) ? table_dev : nullptr;
-    m.first_row = m.tab ? table_dev + (int64_t)nrows * SF_ERASE_ROW_WORDS : nullptr;
-    hipLaunchKernelGGL(sf_pack_clip_u8_sample_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, m);
-    return check_launch("pack_clip_u8_sample");
+    const PackCrop crop = {crop_host, crop_dev, S};
+    const PackErase erase = {erase_mode, table_host, table_dev, nrows, table_words};
+    const PackMix mix = {mix_mode, lam, one_minus_lam, yl, yh, xl, xh};
+    return pack_clip_impl("sf_pack_clip_u8_sample", frames, N, Tin, Hs, Ws, t_index, Tout, mean0, mean1, mean2, std0, std1, std2,
+                          reverse, out, &crop, &erase, &mix, stream);
 }
 
 // ================================================================================================

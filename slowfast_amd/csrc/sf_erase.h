@@ -1,11 +1,10 @@
 // Random erasing of a training batch on the device (slowfast/datasets/random_erasing.py; datasets/kinetics.py:437-447 erases
 // the normalised fp32 clip on the host just before pack_pathway_output).  The draw stays on the host
-// (slowfast_amd/random_erasing.py) and arrives as ONE table; two streaming kernels apply it:
+// (slowfast_amd/random_erasing.py) and arrives as ONE table; the two streaming kernels of sf_erase_clip_f32 apply it to a dense fp32 (N, C, T, H, W) batch: in place
+// (only erased elements are written, nothing is read), or into another buffer (every element read once and written once).
 //
-//   sf_erase_clip_f32    a dense fp32 (N, C, T, H, W) batch: in place (only erased elements are written, nothing is read), or
-//                        into another buffer (every element read once and written once)
-//   sf_pack_clip_u8_aug  sf_pack_clip_u8 (sf_pool.h) with erasing, then optional MixUp / CutMix (mix2() of sf_mixup.h), in fp32
-//                        between the normalisation and the 16-bit rounding
+// The packed uint8 path (sf_pack_clip_u8_aug and sf_pack_clip_u8_sample, sf_pack.h) erases with erase_find() and erase_value1()
+// of this file, in fp32 between the normalisation and the mixing.
 //
 // The table (int32 words, one host-to-device copy):  R rows of SF_ERASE_ROW_WORDS words
 //     [0] n  [1] t0  [2] t1  [3] top  [4] left  [5] h  [6] w  [7] key_lo  [8] key_hi  [9] colour word offset  [10] end  [11] 0
@@ -15,8 +14,8 @@
 //
 // Overlap.  The reference assigns the boxes of a sample one after the other, so the LAST row that contains an element decides
 // its value.  No kernel relies on store order for that: the in-place kernel gives every row its own slice of the grid and a
-// thread skips an element that a later row of the same sample contains (that row's slice writes it), the other two kernels
-// search the sample's rows from the last one down.  Every erased element is therefore stored exactly once.
+// thread skips an element that a later row of the same sample contains (that row's slice writes it), the copy kernel and
+// the packed path search the sample's rows from the last one down.  Every erased element is therefore stored exactly once.
 //
 // Element identity.  A value depends on (row, c, t, y, x) of the NORMALISED clip only: idx = ((c * T + t) * H + y) * W + x
 // with t the source frame and c the channel in DATA.MEAN order -- before pathway selection and channel reversal, so the Slow
@@ -29,8 +28,6 @@
 // between the device, the host simulator and the float64 restatement of the tests.
 #pragma once
 #include "sf_common.h"
-#include "sf_pool.h"
-#include "sf_mixup.h"
 
 #define SF_ERASE_ROW_WORDS 12
 enum { SF_ERASE_CONST = 0, SF_ERASE_RAND = 1, SF_ERASE_PIXEL = 2 };
@@ -224,58 +221,5 @@ __global__ __launch_bounds__(SF_THREADS) void sf_erase_copy_kernel(EraseClipPara
         }
         if (vec && cnt == 4) *reinterpret_cast<f32x4*>(out + base) = v;
         else for (int k = 0; k < cnt; ++k) out[base + k] = v[k];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// sf_pack_clip_u8_mix_kernel (sf_mixup.h) with every sample erased by its own rows before the blend: one thread per output
-// pixel; value(n) = the deciding row's value for (sc, ts, h, w) of sample n, or the normalised frame; mixup blends value(n)
-// with value(N-1-n) through mix2(), cutmix takes value(N-1-n) inside the box, mix < 0 is erasing alone.
-struct PackClipAugParams {
-    PackClipParams k;
-    int H, W;
-    int mix;                // -1 none, 0 mixup, 1 cutmix
-    float lam, oml;
-    int yl, yh, xl, xh;
-    int erase_mode;
-    const int* tab;         // null: no erasing
-    const int* first_row;
-    FastDiv fdW;
-};
-__device__ __forceinline__ float pack_clip_aug_value(const PackClipAugParams& m, const unsigned char* px, int row, int sc, int ts,
-                                                     int h, int w) {
-    if (row < 0) return pack_clip_norm(px, sc, m.k);
-    const uint64_t idx = (((uint64_t)sc * m.k.Tin + ts) * m.H + h) * m.W + w;
-    return erase_value1(m.tab, row, m.erase_mode, 3, sc, ts, idx);
-}
-__global__ __launch_bounds__(SF_THREADS) void sf_pack_clip_u8_aug_kernel(PackClipAugParams m) {
-    const PackClipParams& p = m.k;
-    for (int64_t idx = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x; idx < p.total; idx += (int64_t)gridDim.x * SF_THREADS) {
-        uint32_t q, hw, n, to, h, w;
-        fd_divmod((uint32_t)idx, p.fdHW, q, hw);
-        fd_divmod(q, p.fdT, n, to);
-        fd_divmod(hw, m.fdW, h, w);
-        const int ts = p.t_index ? p.t_index[to] : (int)to;
-        const int64_t pix = ((int64_t)ts * p.HW + hw) * 3;
-        const int no = p.N - 1 - (int)n;
-        const bool inbox = (int)h >= m.yl && (int)h < m.yh && (int)w >= m.xl && (int)w < m.xh;
-        const bool need_self = m.mix != 1 || !inbox, need_other = m.mix == 0 || (m.mix == 1 && inbox);
-        const unsigned char* self = p.frames + (int64_t)n * p.Tin * p.HW * 3 + pix;
-        const unsigned char* other = p.frames + (int64_t)no * p.Tin * p.HW * 3 + pix;
-        const int rs = (m.tab && need_self) ? erase_find(m.tab, m.first_row, (int)n, ts, (int)h, (int)w) : -1;
-        const int ro = (m.tab && need_other) ? erase_find(m.tab, m.first_row, no, ts, (int)h, (int)w) : -1;
-        f16x4 o;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int sc = p.reverse ? 2 - c : c;           // normalisation and erasing happen before the channel reversal
-            float v;
-            if (m.mix == 0) v = mix2(pack_clip_aug_value(m, self, rs, sc, ts, (int)h, (int)w),
-                                     pack_clip_aug_value(m, other, ro, sc, ts, (int)h, (int)w), m.lam, m.oml);
-            else if (need_other) v = pack_clip_aug_value(m, other, ro, sc, ts, (int)h, (int)w);
-            else v = pack_clip_aug_value(m, self, rs, sc, ts, (int)h, (int)w);
-            o[c] = (f16)v;
-        }
-        o[3] = (f16)0;
-        *reinterpret_cast<f16x4*>(p.out + idx * 4) = o;
     }
 }

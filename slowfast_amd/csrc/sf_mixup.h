@@ -1,9 +1,11 @@
 // MixUp / CutMix of a training batch on the device (slowfast/datasets/mixup.py; tools/train_net.py:109-111 mixes inputs[0]
-// and the labels between the loader and the forward pass).  Three streaming kernels, launched eagerly with scalar arguments:
+// and the labels between the loader and the forward pass).  Streaming kernels, launched eagerly with scalar arguments:
 //
 //   sf_mix_clip_f32      the reference contract on a dense fp32 (B, C, T, H, W) clip, in place or into another buffer
-//   sf_pack_clip_u8_mix  sf_pack_clip_u8 (sf_pool.h) with the mixing between the fp32 normalisation and the 16-bit rounding
 //   sf_mix_targets       mixup_target(): two smoothed one-hot rows blended into a (B, K) fp32 buffer
+//
+// The packed uint8 path (sf_pack_clip_u8_mix and later, sf_pack.h) mixes with the mix2() of this file between the fp32
+// normalisation and the 16-bit rounding.
 //
 // Arithmetic.  `x.mul_(lam).add_(x.flip(0).mul_(1 - lam))` is three separately rounded fp32 operations with lam and 1 - lam
 // rounded to fp32 from the host's doubles; hipcc contracts a * b + c into an FMA by default, which is a different number.  Every
@@ -15,7 +17,6 @@
 // (mixup: fl(x*lam) + fl(x*oml), computed and stored once -- not the identity; cutmix: untouched).
 #pragma once
 #include "sf_common.h"
-#include "sf_pool.h"
 
 // fl(fl(a * lam) + fl(b * oml))
 __device__ __forceinline__ float mix2(float a, float b, float lam, float oml) {
@@ -132,49 +133,6 @@ __global__ __launch_bounds__(SF_THREADS) void sf_cutmix_copy_kernel(MixClipParam
             const int xb = x0 + 4 < p.W ? x0 + 4 : p.W;
             for (int x = x0; x < xb; ++x) out[row + x] = ((yin && x >= p.xl && x < p.xh) ? other : self)[row + x];
         }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// sf_pack_clip_u8_kernel (sf_pool.h) with the batch mixed between the normalisation and the rounding to the storage type:
-// one thread per output pixel reads frame n and -- for mixup, or inside the cutmix box -- frame N-1-n, normalises each in
-// fp32 exactly as the unmixed kernel does, blends with mix2() and rounds once.  A W pair (16 bytes) is written by two
-// threads, so a box edge at an odd column needs no special case.
-struct PackClipMixParams {
-    PackClipParams k;
-    int W;
-    int mode;               // 0 mixup, 1 cutmix
-    float lam, oml;
-    int yl, yh, xl, xh;
-    FastDiv fdW;
-};
-__device__ __forceinline__ float pack_clip_norm(const unsigned char* src, int sc, const PackClipParams& p) {
-    const float v = (float)src[sc] / 255.0f;
-    return (v - p.mean[sc]) / p.stdv[sc];
-}
-__global__ __launch_bounds__(SF_THREADS) void sf_pack_clip_u8_mix_kernel(PackClipMixParams m) {
-    const PackClipParams& p = m.k;
-    for (int64_t idx = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x; idx < p.total; idx += (int64_t)gridDim.x * SF_THREADS) {
-        uint32_t q, hw, n, to, h, w;
-        fd_divmod((uint32_t)idx, p.fdHW, q, hw);
-        fd_divmod(q, p.fdT, n, to);
-        fd_divmod(hw, m.fdW, h, w);
-        const int ts = p.t_index ? p.t_index[to] : (int)to;
-        const int64_t pix = ((int64_t)ts * p.HW + hw) * 3;
-        const unsigned char* self = p.frames + (int64_t)n * p.Tin * p.HW * 3 + pix;
-        const unsigned char* other = p.frames + (int64_t)(p.N - 1 - (int)n) * p.Tin * p.HW * 3 + pix;
-        const bool inbox = (int)h >= m.yl && (int)h < m.yh && (int)w >= m.xl && (int)w < m.xh;
-        f16x4 o;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int sc = p.reverse ? 2 - c : c;           // normalisation happens before the channel reversal
-            float v;
-            if (m.mode == 0) v = mix2(pack_clip_norm(self, sc, p), pack_clip_norm(other, sc, p), m.lam, m.oml);
-            else v = pack_clip_norm(inbox ? other : self, sc, p);
-            o[c] = (f16)v;
-        }
-        o[3] = (f16)0;
-        *reinterpret_cast<f16x4*>(p.out + idx * 4) = o;
     }
 }
 

@@ -1,13 +1,14 @@
 // Spatial sampling of a training batch on the device (slowfast/datasets/utils.py:114-185 spatial_sampling, applied at
 // datasets/kinetics.py:410-435 to the normalised fp32 clip: short-side scale jitter or random resized crop -- a bilinear
 // F.interpolate of every frame -- then a crop and a horizontal flip).  The draw stays on the host
-// (slowfast_amd/spatial_sampling.py) and arrives as ONE table with a row per sample; two gather kernels apply it to the
-// decoded uint8 frames:
+// (slowfast_amd/spatial_sampling.py) and arrives as ONE table with a row per sample; sample_pixel() applies it to the decoded
+// uint8 frames for two sinks:
 //
 //   sf_sample_clip_u8       uint8 (N, T, Hs, Ws, 3) -> dense fp32 [N][3][T][S][S], the layout sf_erase_clip_f32 and
-//                           sf_mix_clip_f32 work on in place
-//   sf_pack_clip_u8_sample  sf_pack_clip_u8_aug (sf_erase.h) with every sample -- and its mixing partner -- sampled through its
-//                           own row first: sample, erase, mix in fp32, one rounding into the stems' W-pair buffer
+//                           sf_mix_clip_f32 work on in place (the kernel below)
+//   sf_pack_clip_u8_sample  the packed path (sf_pack.h) with PackSampled as its pixel source: every sample -- and its mixing
+//                           partner -- sampled through its own row, then erased and mixed in fp32, one rounding into the stems'
+//                           W-pair buffer
 //
 // The table (int32 words, one host-to-device copy): N rows of SF_CROP_ROW_WORDS words
 //     [0] src_h [1] src_w   valid size of the sample's frames inside the padded Hs x Ws buffer
@@ -34,9 +35,7 @@
 // exchanging them between lanes would.
 #pragma once
 #include "sf_common.h"
-#include "sf_pool.h"
-#include "sf_mixup.h"
-#include "sf_erase.h"
+#include "sf_pack.h"
 
 #define SF_CROP_ROW_WORDS 12
 
@@ -61,14 +60,9 @@ __device__ __forceinline__ float sample_blend(float a, float b, float c, float d
     return ay.l0 * top + ay.l1 * bot;
 }
 
-struct SampleGeom {
-    const int* crop;            // device copy of the table
-    int Hs, Ws, S;              // padded source frame, output size
-    FastDiv fdS;                // plane index -> (oy, ox)
-};
 // normalised, resized, cropped, flipped value of output pixel (oy, ox) of source frame ts of sample n: channels in DATA.MEAN order
-__device__ __forceinline__ void sample_pixel(const PackClipParams& p, const SampleGeom& g, int n, int ts, int oy, int ox,
-                                             float (&v)[3]) {
+__device__ __forceinline__ void sample_pixel(const PackClipParams& p, int n, int ts, int oy, int ox, float (&v)[3]) {
+    const SampleGeom& g = p.g;
     const int* c = g.crop + (int64_t)n * SF_CROP_ROW_WORDS;
     const int win_y = c[2], win_x = c[3], win_h = c[4], win_w = c[5], res_h = c[6], res_w = c[7], off_y = c[8], off_x = c[9];
     const int flip = c[10];
@@ -87,8 +81,7 @@ __device__ __forceinline__ void sample_pixel(const PackClipParams& p, const Samp
 // ------------------------------------------------------------------------------------------------
 // dense fp32 clip: one thread per output pixel, three stores of 4 bytes a channel plane apart (lanes along x: 256-byte runs)
 struct SampleClipParams {
-    PackClipParams k;           // frames, N, Tin == Tout, HW = S * S, mean / stdv, total = N * T * S * S, fdHW, fdT
-    SampleGeom g;
+    PackClipParams k;           // frames, N, Tin == Tout, HW = S * S, mean / stdv, total = N * T * S * S, fdHW, fdT, fdW, g
     float* dst;                 // [N][3][T][S][S]
 };
 __global__ __launch_bounds__(SF_THREADS) void sf_sample_clip_u8_kernel(SampleClipParams m) {
@@ -98,9 +91,9 @@ __global__ __launch_bounds__(SF_THREADS) void sf_sample_clip_u8_kernel(SampleCli
         uint32_t q, hw, n, t, oy, ox;
         fd_divmod((uint32_t)idx, p.fdHW, q, hw);
         fd_divmod(q, p.fdT, n, t);
-        fd_divmod(hw, m.g.fdS, oy, ox);
+        fd_divmod(hw, p.fdW, oy, ox);
         float v[3];
-        sample_pixel(p, m.g, (int)n, (int)t, (int)oy, (int)ox, v);
+        sample_pixel(p, (int)n, (int)t, (int)oy, (int)ox, v);
         float* o = m.dst + ((int64_t)n * 3 * p.Tin + t) * p.HW + hw;
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c * plane] = v[c];
@@ -108,45 +101,9 @@ __global__ __launch_bounds__(SF_THREADS) void sf_sample_clip_u8_kernel(SampleCli
 }
 
 // ------------------------------------------------------------------------------------------------
-// sf_pack_clip_u8_aug_kernel with value(n) = the deciding erase row's value for (sc, ts, oy, ox) of the CROPPED clip
-// (T, 3, S, S), or the sampled pixel of sample n under ITS crop row; one thread per output pixel.
-struct SamplePackParams {
-    PackClipParams k;           // HW = S * S, total = N * Tout * S * S
-    SampleGeom g;
-    int mix;                    // -1 none, 0 mixup, 1 cutmix
-    float lam, oml;
-    int yl, yh, xl, xh;
-    int erase_mode;
-    const int* tab;             // null: no erasing
-    const int* first_row;
-};
-__global__ __launch_bounds__(SF_THREADS) void sf_pack_clip_u8_sample_kernel(SamplePackParams m) {
-    const PackClipParams& p = m.k;
-    const int S = m.g.S;
-    for (int64_t idx = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x; idx < p.total; idx += (int64_t)gridDim.x * SF_THREADS) {
-        uint32_t q, hw, n, to, oy, ox;
-        fd_divmod((uint32_t)idx, p.fdHW, q, hw);
-        fd_divmod(q, p.fdT, n, to);
-        fd_divmod(hw, m.g.fdS, oy, ox);
-        const int ts = p.t_index ? p.t_index[to] : (int)to;
-        const int no = p.N - 1 - (int)n;
-        const bool inbox = (int)oy >= m.yl && (int)oy < m.yh && (int)ox >= m.xl && (int)ox < m.xh;
-        const bool need_self = m.mix != 1 || !inbox, need_other = m.mix == 0 || (m.mix == 1 && inbox);
-        const int rs = (m.tab && need_self) ? erase_find(m.tab, m.first_row, (int)n, ts, (int)oy, (int)ox) : -1;
-        const int ro = (m.tab && need_other) ? erase_find(m.tab, m.first_row, no, ts, (int)oy, (int)ox) : -1;
-        float a[3] = {0.0f, 0.0f, 0.0f}, b[3] = {0.0f, 0.0f, 0.0f};
-        if (need_self && rs < 0) sample_pixel(p, m.g, (int)n, ts, (int)oy, (int)ox, a);
-        if (need_other && ro < 0) sample_pixel(p, m.g, no, ts, (int)oy, (int)ox, b);
-        f16x4 o;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int sc = p.reverse ? 2 - c : c;           // sampling and erasing happen before the channel reversal
-            const uint64_t e = (((uint64_t)sc * p.Tin + ts) * S + oy) * S + ox;
-            const float vs = rs < 0 ? (p.reverse ? a[2 - c] : a[c]) : erase_value1(m.tab, rs, m.erase_mode, 3, sc, ts, e);
-            const float vo = ro < 0 ? (p.reverse ? b[2 - c] : b[c]) : erase_value1(m.tab, ro, m.erase_mode, 3, sc, ts, e);
-            o[c] = (f16)(m.mix == 0 ? mix2(vs, vo, m.lam, m.oml) : (need_other ? vo : vs));
-        }
-        o[3] = (f16)0;
-        *reinterpret_cast<f16x4*>(p.out + idx * 4) = o;
+// pixel source of sf_pack_clip_kernel (sf_pack.h): sample n under ITS crop row
+struct PackSampled {
+    static __device__ __forceinline__ void pixel(const PackClipParams& p, int n, int ts, uint32_t, int oy, int ox, float (&v)[3]) {
+        sample_pixel(p, n, ts, oy, ox, v);
     }
-}
+};

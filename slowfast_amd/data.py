@@ -49,99 +49,66 @@ def pack_pathways_u8(frames, cfg, out=None, mix=None, erase=None, crop=None):
     reference's order (datasets/kinetics.py:402-449).  ``erase`` must then be drawn for the CROPPED clip (T, 3, S, S), the
     cutmix box of ``mix`` lies in the S x S plane, and the mixing partner is sampled with its own row before the blend.
     ``crop=None`` reaches the kernels above exactly as before."""
-    if crop is not None:
-        return _pack_pathways_u8_sample(frames, cfg, out, mix, erase, crop)
-    assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3 and frames.shape[3] % 2 == 0
-    frames = frames.contiguous()
-    N, T, H, W, _ = frames.shape
-    mean, std = [float(v) for v in cfg.DATA.MEAN], [float(v) for v in cfg.DATA.STD]
-    dst, out = out, []
-    tab = None
-    if erase is not None and len(erase.rows):
-        from . import random_erasing
-        if tuple(erase.shape) != (T, 3, H, W):
-            raise _sflib.SfError("pack_pathways_u8: the erase table was drawn for (T, C, H, W) = %s, the frames are %s" % (
-                tuple(erase.shape), (T, 3, H, W)))
-        ops._stream(frames)
-        tab = random_erasing.upload_table(erase, N, frames.device) + (random_erasing.MODES[erase.mode],)
-    for i, idx in enumerate(pathway_frame_indices(cfg, T)):
-        Tout = T if idx is None else int(idx.numel())
-        idx_dev = None if idx is None else idx.to(device=frames.device, dtype=torch.int32).contiguous()
-        if dst is None:
-            base = torch.empty((N, Tout, H, W // 2, 8), dtype=_f16, device=frames.device)
-        else:
-            base = dst[i].permute(0, 2, 3, 4, 1)
-            assert tuple(base.shape) == (N, Tout, H, W // 2, 8) and base.is_contiguous() and base.dtype == _f16, \
-                "out[i] must be a tensor a previous pack_pathways_u8 call returned for the same clip geometry"
-        mixing = i == 0 and mix is not None and mix.lam != 1.0
-        if tab is not None:
-            host, dev, rows, emode = tab
-            lam = float(mix.lam) if mixing else 1.0
-            yl, yh, xl, xh = mix.box if mixing and mix.use_cutmix else (0, 0, 0, 0)
-            get_lib().call("sf_pack_clip_u8_aug", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1],
-                           mean[2], std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(), emode,
-                           host.ctypes.data, dev.data_ptr(), rows, int(host.size),
-                           int(bool(mix.use_cutmix)) if mixing else -1, lam, 1.0 - lam, int(yl), int(yh), int(xl), int(xh),
-                           ops._stream(frames),
-                           work=dict(bytes=(6.0 if mixing and not mix.use_cutmix else 3.0) * N * Tout * H * W
-                                     + 2.0 * base.numel()))
-        elif mixing:
-            lam = float(mix.lam)
-            yl, yh, xl, xh = mix.box if mix.use_cutmix else (0, 0, 0, 0)
-            get_lib().call("sf_pack_clip_u8_mix", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1],
-                           mean[2], std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(),
-                           int(bool(mix.use_cutmix)), lam, 1.0 - lam, int(yl), int(yh), int(xl), int(xh), ops._stream(frames),
-                           work=dict(bytes=(3.0 if mix.use_cutmix else 6.0) * N * Tout * H * W + 2.0 * base.numel()))
-        else:
-            get_lib().call("sf_pack_clip_u8", frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1], mean[2],
-                           std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(),
-                           ops._stream(frames), work=dict(bytes=3.0 * N * Tout * H * W + 2.0 * base.numel()))
-        x = base.permute(0, 4, 1, 2, 3)
-        x._sf_wpairs = True                 # already the operand layout of engine.StemConvUnit
-        out.append(x)
-    return out
-
-
-def _pack_pathways_u8_sample(frames, cfg, dst, mix, erase, crop):
-    """pack_pathways_u8 with a crop table: one sf_pack_clip_u8_sample launch per pathway.  Everything is checked before the
-    first launch; a rejected call raises SfError."""
     from . import random_erasing, spatial_sampling
-    stream = spatial_sampling.check_frames(frames, "pack_pathways_u8")
-    N, T, Hs, Ws, _ = frames.shape
-    S = int(crop.crop_size)
-    if S <= 0 or S % 2:
-        raise _sflib.SfError("pack_pathways_u8: the crop size must be even (got %d)" % S)
     mean, std = [float(v) for v in cfg.DATA.MEAN], [float(v) for v in cfg.DATA.STD]
-    chost, cdev = spatial_sampling.upload_table(crop, N, frames.device)
+    if crop is None:
+        assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3 and frames.shape[3] % 2 == 0
+        frames = frames.contiguous()
+        stream = ops._stream(frames)
+        N, T, H, W, _ = frames.shape
+        Ho, Wo, clip = H, W, "frames are"
+    else:                                   # everything is checked before the first launch; a rejected call raises SfError
+        stream = spatial_sampling.check_frames(frames, "pack_pathways_u8")
+        N, T, H, W, _ = frames.shape
+        Ho = Wo = int(crop.crop_size)
+        if Ho <= 0 or Ho % 2:
+            raise _sflib.SfError("pack_pathways_u8: the crop size must be even (got %d)" % Ho)
+        chost, cdev = spatial_sampling.upload_table(crop, N, frames.device)
+        clip = "cropped clip is"
     ehost = edev = None
     rows = words = emode = 0
     if erase is not None and len(erase.rows):
-        if tuple(erase.shape) != (T, 3, S, S):
-            raise _sflib.SfError("pack_pathways_u8: the erase table was drawn for (T, C, H, W) = %s, the cropped clip is %s" % (
-                tuple(erase.shape), (T, 3, S, S)))
+        if tuple(erase.shape) != (T, 3, Ho, Wo):
+            raise _sflib.SfError("pack_pathways_u8: the erase table was drawn for (T, C, H, W) = %s, the %s %s" % (
+                tuple(erase.shape), clip, (T, 3, Ho, Wo)))
         ehost, edev, rows = random_erasing.upload_table(erase, N, frames.device)
         words, emode = int(ehost.size), random_erasing.MODES[erase.mode]
-    out = []
+    dst, out = out, []
     for i, idx in enumerate(pathway_frame_indices(cfg, T)):
         Tout = T if idx is None else int(idx.numel())
         idx_dev = None if idx is None else idx.to(device=frames.device, dtype=torch.int32).contiguous()
         if dst is None:
-            base = torch.empty((N, Tout, S, S // 2, 8), dtype=_f16, device=frames.device)
+            base = torch.empty((N, Tout, Ho, Wo // 2, 8), dtype=_f16, device=frames.device)
         else:
             base = dst[i].permute(0, 2, 3, 4, 1)
-            if not (tuple(base.shape) == (N, Tout, S, S // 2, 8) and base.is_contiguous() and base.dtype == _f16):
+            fits = tuple(base.shape) == (N, Tout, Ho, Wo // 2, 8) and base.is_contiguous() and base.dtype == _f16
+            if crop is None:
+                assert fits, "out[i] must be a tensor a previous pack_pathways_u8 call returned for the same clip geometry"
+            elif not fits:
                 raise _sflib.SfError("pack_pathways_u8: out[%d] must be a tensor a previous call returned for the same cropped "
                                      "clip geometry" % i)
         mixing = i == 0 and mix is not None and mix.lam != 1.0
         lam = float(mix.lam) if mixing else 1.0
-        yl, yh, xl, xh = mix.box if mixing and mix.use_cutmix else (0, 0, 0, 0)
-        get_lib().call("sf_pack_clip_u8_sample", frames.data_ptr(), N, T, Hs, Ws, ops._ptr(idx_dev), Tout, mean[0], mean[1],
-                       mean[2], std[0], std[1], std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(),
-                       chost.ctypes.data, cdev.data_ptr(), S, emode, None if ehost is None else ehost.ctypes.data,
-                       ops._ptr(edev), rows, words, int(bool(mix.use_cutmix)) if mixing else -1, lam, 1.0 - lam, int(yl),
-                       int(yh), int(xl), int(xh), stream,
-                       work=dict(bytes=(24.0 if mixing and not mix.use_cutmix else 12.0) * N * Tout * S * S
-                                 + 2.0 * base.numel()))
+        box = [int(v) for v in (mix.box if mixing and mix.use_cutmix else (0, 0, 0, 0))]
+        # the entry point with the fewest stages that holds this call's, and its argument list after ``out``
+        tail = [int(bool(mix.use_cutmix)) if mixing else -1, lam, 1.0 - lam] + box
+        etail = [emode, None if ehost is None else ehost.ctypes.data, ops._ptr(edev), rows, words]
+        pixels = float(N * Tout * Ho * Wo)
+        if crop is not None:                # four taps of three bytes per sampled pixel, of the partner too under mixup
+            name, tail = "sf_pack_clip_u8_sample", [chost.ctypes.data, cdev.data_ptr(), Ho] + etail + tail
+            read = (24.0 if mixing and not mix.use_cutmix else 12.0) * pixels
+        elif ehost is not None:
+            name, tail = "sf_pack_clip_u8_aug", etail + tail
+            read = (6.0 if mixing and not mix.use_cutmix else 3.0) * pixels
+        elif mixing:
+            name = "sf_pack_clip_u8_mix"
+            read = (3.0 if mix.use_cutmix else 6.0) * pixels
+        else:
+            name, tail = "sf_pack_clip_u8", []
+            read = 3.0 * pixels
+        get_lib().call(name, frames.data_ptr(), N, T, H, W, ops._ptr(idx_dev), Tout, mean[0], mean[1], mean[2], std[0], std[1],
+                       std[2], int(bool(cfg.DATA.REVERSE_INPUT_CHANNEL)), base.data_ptr(), *tail, stream,
+                       work=dict(bytes=read + 2.0 * base.numel()))
         x = base.permute(0, 4, 1, 2, 3)
         x._sf_wpairs = True                 # already the operand layout of engine.StemConvUnit
         out.append(x)

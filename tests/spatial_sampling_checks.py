@@ -247,6 +247,58 @@ def check_pack_without_crop(device):
                                  0, 0, 0, 0))
 
 
+def words16(x):
+    """The 16-bit storage words of a packed tensor."""
+    return x.contiguous().view(torch.int16).cpu()
+
+
+def check_pack_entry_points_agree(device):
+    """The four packed entry points are one computation with stages switched off, so where their stages coincide their outputs
+    are equal bit for bit on the storage words: (1) an identity crop row (nothing resized, nothing cut, no flip) makes
+    sf_pack_clip_u8_sample the crop=None call, under every erase mode and mixing; (2) sf_pack_clip_u8_aug without an erase
+    table and without mixing is sf_pack_clip_u8; (3) without an erase table and with mixing it is sf_pack_clip_u8_mix.
+    N = 3 is odd (the middle sample is its own partner), 3 * 3 * 144 pixels are five workgroups and a tail of 16, and the
+    cutmix box has odd column edges."""
+    N, H = 3, 12
+    identity = ss.make_table([sa.CropRow(H, H, 0, 0, H, H, H, H, 0, 0, 0)] * N, H)
+    mixes = (None, MixParams(0.3, False, None), MixParams(0.3, True, (3, 9, 5, 11)))
+    for preset, T in (("C2D_8x8_R50", 3), ("SLOWFAST_8x8_R50", 8)):
+        frames = torch.randint(0, 256, (N, T, H, H, 3), generator=torch.Generator().manual_seed(17 + T), dtype=torch.int64)
+        fd = frames.to(torch.uint8).to(device)
+        for reverse in (False, True):
+            cfg = sa.get_preset(preset, ["DATA.MEAN", MEAN, "DATA.STD", STD, "DATA.REVERSE_INPUT_CHANNEL", reverse])
+            for mode in (None, "const", "rand", "pixel"):
+                table = None
+                if mode is not None:
+                    random.seed(N)
+                    torch.manual_seed(N)
+                    table = sa.RandomErasing(probability=1.0, mode=mode, max_count=2, noise_seed=11).sample_batch(N, (T, 3, H, H))
+                    assert len(table.rows) >= N
+                for mix in mixes:
+                    got = sa.pack_pathways_u8(fd, cfg, crop=identity, erase=table, mix=mix)
+                    want = sa.pack_pathways_u8(fd, cfg, erase=table, mix=mix)
+                    assert len(got) == len(want) == (2 if preset.startswith("SLOWFAST") else 1)
+                    for p, (g, w_) in enumerate(zip(got, want)):
+                        assert g.shape == w_.shape and torch.equal(words16(g), words16(w_)), (preset, reverse, mode, mix, p)
+
+    T = 3
+    fd = torch.randint(0, 256, (N, T, H, H, 3), generator=torch.Generator().manual_seed(5), dtype=torch.int64).to(torch.uint8).to(device)
+    stream = sa.ops._stream(fd)
+    lib = _sflib.get_lib()
+    head = (fd.data_ptr(), N, T, H, H, None, T, MEAN[0], MEAN[1], MEAN[2], STD[0], STD[1], STD[2], 0)
+    lam, oml = mixup._f32_pair(0.3)
+    no_table = (0, None, None, 0, 0)
+
+    def direct(name, *tail):
+        out = torch.zeros((N, T, H, H // 2, 8), dtype=ACT, device=fd.device)
+        lib.call(name, *head, out.data_ptr(), *tail, stream)
+        return words16(out)
+
+    assert torch.equal(direct("sf_pack_clip_u8_aug", *no_table, -1, 1.0, 0.0, 0, 0, 0, 0), direct("sf_pack_clip_u8"))
+    for mix_tail in ((0, lam, oml, 0, 0, 0, 0), (1, lam, oml, 3, 9, 5, 11)):
+        assert torch.equal(direct("sf_pack_clip_u8_aug", *no_table, *mix_tail), direct("sf_pack_clip_u8_mix", *mix_tail)), mix_tail
+
+
 def generator_state():
     """Python's and numpy's global generator states, comparable with ==."""
     s = np.random.get_state()

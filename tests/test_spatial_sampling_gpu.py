@@ -32,6 +32,10 @@ def test_pack_without_crop_is_unchanged(gpu):
     checks.check_pack_without_crop(gpu)
 
 
+def test_pack_entry_points_agree(gpu):
+    checks.check_pack_entry_points_agree(gpu)
+
+
 def test_rejects(gpu):
     checks.check_rejects(gpu)
     checks.check_host_tensor_rejected()

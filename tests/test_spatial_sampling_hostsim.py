@@ -30,6 +30,10 @@ def test_pack_without_crop_is_unchanged(sim):
     checks.check_pack_without_crop(sim)
 
 
+def test_pack_entry_points_agree(sim):
+    checks.check_pack_entry_points_agree(sim)
+
+
 def test_rejects(sim):
     checks.check_rejects(sim)
 

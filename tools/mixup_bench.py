@@ -1,4 +1,5 @@
-"""Microbenchmark of the MixUp / CutMix entry points (csrc/sf_mixup.h) at the MViTv2-S bs32 clip (32, 3, 16, 224, 224),
+"""Microbenchmark of the MixUp / CutMix entry points (csrc/sf_mixup.h; the pack_u8 rows are specialisations of
+sf_pack_clip_kernel, csrc/sf_pack.h) at the MViTv2-S bs32 clip (32, 3, 16, 224, 224),
 HIP-event timed with COLD operands: every call works on the next of several clips whose sum exceeds the 256 MiB Infinity Cache
 (the rotation of tools/optim_bench.py):
   mixup_inplace     sf_mix_clip_f32 mode 0, in place                     (reads + writes the clip once: 2 x 308 MB)

@@ -1,4 +1,5 @@
-"""Microbenchmark of the random-erasing entry points (csrc/sf_erase.h) at an (8, 3, 16, 224, 224) batch, `pixel` mode, one
+"""Microbenchmark of the random-erasing entry points (csrc/sf_erase.h; the pack_u8 rows are specialisations of
+sf_pack_clip_kernel, csrc/sf_pack.h) at an (8, 3, 16, 224, 224) batch, `pixel` mode, one
 112 x 112 box (a quarter of the frame, unaligned corner) over all frames of every sample.  HIP-event timed with COLD operands:
 every call works on the next of several batches whose sum exceeds the 256 MiB Infinity Cache (the rotation of
 tools/mixup_bench.py):

@@ -1,10 +1,12 @@
-"""Microbenchmark of the spatial-sampling entry points (csrc/sf_sample.h): uint8 (8, 16, 256, 340, 3) decoded frames -> 224 x 224,
+"""Microbenchmark of the spatial-sampling entry points (csrc/sf_sample.h; the pack_u8 rows are specialisations of
+sf_pack_clip_kernel, csrc/sf_pack.h): uint8 (8, 16, 256, 340, 3) decoded frames -> 224 x 224,
 short-side jitter to 288 (288 x 382 resized), crop at an unaligned offset, every other sample flipped.  HIP-event timed with COLD
 operands: every call works on the next of several buffer sets whose sum exceeds the 256 MiB Infinity Cache (the rotation of
 tools/random_erasing_bench.py):
   sample_clip_kernel   sf_sample_clip_u8, table already on the device     uint8 frames -> dense fp32 (N, 3, T, S, S)
   sample_clip          spatial_sampling.sample_clip: the same with the table packed and uploaded per call
   pack_u8_sample       pack_pathways_u8(crop=): uint8 frames -> 16-bit W-pair clip, sampled while packing
+                       (sf_pack_clip_u8_sample: sf_pack_clip_kernel<PackSampled, true, true>)
   pack_u8_sample_aug   the same with an erase table (pixel mode) and mixup
   pack_u8              sf_pack_clip_u8 on frames that are already 224 x 224 (what the sampling is added to)
   torch_sample         the yardstick: the normalised fp32 clip is already on the device; per sample F.interpolate (bilinear,
