@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 28
+#define SF_ABI_VERSION 29
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -496,6 +496,30 @@ int sf_color_frame_means_f32(const float* clip, int32_t N, int32_t T, int64_t HW
 int sf_color_clip_f32(float* clip, int32_t N, int32_t T, int64_t HW, const int32_t* table_host, const int32_t* table_dev,
                       const float* means, float mean0, float mean1, float mean2, float std0, float std1, float std2,
                       int32_t reverse, sf_stream_t stream);
+/* RandAugment of the batch on the device (ABI 29) -- replaces the PIL loop of rand_augment_transform(AUG.AA_TYPE) on the decoded
+ * frames (slowfast/datasets/kinetics.py:389-400, datasets/rand_augment.py).  src / dst are dense uint8 [N][T][Hs][Ws][3] buffers
+ * (RGB byte order, every sample padded to the batch's largest frame); one call is one LAYER of the draw.  The layer's table is N
+ * rows of 20 words, given twice as the crop table is: table_host is validated and decides what is launched, table_dev is what
+ * the kernels read.  Layout of a row:
+ *   class (0 copy, 1 lookup table, 2 Color, 3 Sharpness, 4 affine gather), op (0 AutoContrast, 1 Equalize, 2 Invert, 3 Rotate,
+ *   4 Posterize, 5 Solarize, 6 SolarizeAdd, 7 Color, 8 Contrast, 9 Brightness, 10 Sharpness, 11 ShearX, 12 ShearY,
+ *   13 TranslateXRel, 14 TranslateYRel), the integer argument (bits 0 .. 8, threshold 0 .. 256, added value 0 .. 255), the blend
+ *   factor (float bits), the filter (0 bilinear, 1 bicubic), the valid size h, w of the sample's frames, 0, and the six
+ *   coefficients of PIL's inverse affine matrix as fp64 (low word, high word) pairs, computed by the caller.
+ * Inside a sample's h x w region the bytes are PIL's, bit for bit (the arithmetic: csrc/sf_randaug.h); outside it dst is a copy
+ * of src.  Kernel launches only; the only atomics are integer adds: two calls give the same bits.
+ *
+ * sf_randaug_chunk(): the pixels of a frame one workgroup counts / streams.
+ * sf_randaug_hist_u8: hist[(n * T + t) * 1024 + c * 256 + v] = how many valid pixels of frame (n, t) have value v in channel c
+ *   (R, G, B, L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16), for the samples whose row is AutoContrast, Equalize or Contrast;
+ *   the others are left untouched, and with no such row nothing is launched.
+ * sf_randaug_layer_u8: builds the lookup tables of the table rows into lut (N * T * 768 bytes; no such row: not launched, lut
+ *   may be NULL) and streams the layer, src -> dst.  hist may be NULL when no row needs a histogram. */
+int sf_randaug_chunk(void);
+int sf_randaug_hist_u8(const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
+                       const int32_t* table_dev, int32_t* hist, sf_stream_t stream);
+int sf_randaug_layer_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
+                        const int32_t* table_dev, const int32_t* hist, void* lut, sf_stream_t stream);
 /* Stochastic depth -- replaces drop_path() (slowfast/models/common.py:46-59) at the two residual additions of
  * MultiScaleBlock (attention.py:500-510): y[m] = (resid ? resid[m] : 0) + scale[m / rows_per_sample] * x[m], with
  * scale[b] = floor(keep_prob + u_b) / keep_prob sampled by the caller.  Rows are fp16 [M][C], C % 8 == 0. */

@@ -18,4 +18,6 @@ from .spatial_sampling import (SpatialSampling, CropRow, CropTable, construct_sp
 from .spatial_sampling import transform_boxes, collate_boxes, construct_ava_sampling  # noqa: F401,E402  (AVA: boxes follow the crop)
 from .color_augmentation import (ColorAugmentation, ColorRow, ColorTable, construct_color_augmentation,  # noqa: F401,E402
                                  color_clip)  # (colour jitter / PCA lighting / normalisation of the AVA clip on the device)
+from .rand_augment import (RandAugment, AugRow, AugTable, construct_rand_augment,  # noqa: F401,E402
+                           rand_augment_clip)  # (RandAugment of the decoded uint8 frames on the device)
 from .losses import get_loss_func  # noqa: F401,E402

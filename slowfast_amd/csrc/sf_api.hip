@@ -20,6 +20,7 @@
 #include "sf_pack.h"
 #include "sf_sample.h"
 #include "sf_color.h"
+#include "sf_randaug.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2820,6 +2821,89 @@ extern "C" int sf_color_clip_f32(float* clip, int32_t N, int32_t T, int64_t HW, 
     if (vec) hipLaunchKernelGGL(sf_color_clip_kernel<4>, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(sf_color_clip_kernel<1>, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("color_clip_f32");
+}
+
+// ================================================================================================
+// RandAugment of the batch (sf_randaug.h; replaces the PIL loop of rand_augment_transform on the decoded frames,
+// datasets/kinetics.py:389-400).  One call is one LAYER of the draw: a table with a row per sample (layout: sf_randaug.h); the
+// HOST copy is validated and decides what is launched, the kernels read the device copy.  Kernel launches only.
+extern "C" int sf_randaug_chunk(void) { return SF_RANDAUG_CHUNK; }
+// counts the rows that need a histogram / a lookup table; -1 for a bad table
+static int check_randaug_table(const char* who, const int32_t* th, int32_t N, int32_t Hs, int32_t Ws, int& hist_rows, int& lut_rows) {
+    REQUIRE(th, "%s: null table", who);
+    hist_rows = lut_rows = 0;
+    for (int n = 0; n < N; ++n) {
+        const int32_t* w = th + (int64_t)n * SF_RANDAUG_ROW_WORDS;
+        const int cls = w[0], op = w[1];
+        REQUIRE(op >= 0 && op < SF_RANDAUG_OPS, "%s: row %d: unknown op code %d", who, n, op);
+        REQUIRE(cls >= 0 && cls <= 4, "%s: row %d: unknown class %d", who, n, cls);
+        const bool is_lut = op == 0 || op == 1 || op == 2 || op == 4 || op == 5 || op == 6 || op == 8 || op == 9;
+        const bool is_affine = op == 3 || op == 11 || op == 12 || op == 13 || op == 14;
+        REQUIRE(cls == 0 || (cls == 1 && is_lut) || (cls == 2 && op == 7) || (cls == 3 && op == 10) || (cls == 4 && is_affine),
+                "%s: row %d: op %d is not of class %d", who, n, op, cls);
+        REQUIRE(w[5] > 0 && w[5] <= Hs && w[6] > 0 && w[6] <= Ws, "%s: row %d: valid size %d x %d is not inside the %d x %d buffer",
+                who, n, w[5], w[6], Hs, Ws);
+        if (cls == 0) continue;
+        REQUIRE(op != 4 || (w[2] >= 0 && w[2] <= 8), "%s: row %d: Posterize keeps 0 .. 8 bits (got %d)", who, n, w[2]);
+        REQUIRE(op != 5 || (w[2] >= 0 && w[2] <= 256), "%s: row %d: Solarize takes a threshold of 0 .. 256 (got %d)", who, n, w[2]);
+        REQUIRE(op != 6 || (w[2] >= 0 && w[2] <= 255), "%s: row %d: SolarizeAdd adds 0 .. 255 (got %d)", who, n, w[2]);
+        REQUIRE((w[3] & 0x7f800000) != 0x7f800000, "%s: row %d: the blend factor is not a finite float", who, n);
+        if (cls == 4) {
+            REQUIRE(w[4] == 0 || w[4] == 1, "%s: row %d: filter %d is neither 0 (bilinear) nor 1 (bicubic)", who, n, w[4]);
+            for (int k = 0; k < 6; ++k)                     // an exponent of all ones: infinity or NaN
+                REQUIRE((w[9 + 2 * k] & 0x7ff00000) != 0x7ff00000, "%s: row %d: matrix entry %d is not finite", who, n, k);
+        }
+        lut_rows += cls == 1;
+        hist_rows += randaug_needs_hist(cls, op);
+    }
+    return 0;
+}
+static int fill_randaug_params(const char* who, RandAugParams& p, const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
+                               const int32_t* table_dev) {
+    REQUIRE(src && table_dev, "%s: null pointer", who);
+    REQUIRE(N > 0 && T > 0 && (int64_t)N * T <= 65535, "%s: bad shape (N * T must be 1 .. 65535)", who);
+    REQUIRE(Hs > 0 && Ws > 0 && Hs < (1 << 16) && Ws < (1 << 16) && (int64_t)Hs * Ws * 3 < (1ll << 31),
+            "%s: a frame of %d x %d is empty or has 2^31 bytes or more", who, Hs, Ws);
+    memset(&p, 0, sizeof(p));
+    p.src = (const unsigned char*)src; p.table = table_dev; p.N = N; p.T = T; p.Hs = Hs; p.Ws = Ws; p.slab = Hs * Ws;
+    p.fdW = make_fastdiv((uint32_t)Ws);
+    return 0;
+}
+extern "C" int sf_randaug_hist_u8(const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
+                                  const int32_t* table_dev, int32_t* hist, sf_stream_t stream) {
+    RandAugParams p;
+    if (fill_randaug_params("sf_randaug_hist_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
+    int hist_rows, lut_rows;
+    if (check_randaug_table("sf_randaug_hist_u8", table_host, N, Hs, Ws, hist_rows, lut_rows)) return -1;
+    if (hist_rows == 0) return 0;                           // nothing to count: nothing is launched
+    REQUIRE(hist && (uintptr_t)hist % 4 == 0, "sf_randaug_hist_u8: hist must be a 4-byte aligned pointer");
+    p.hist = hist;
+    p.vec = (uintptr_t)src % 16 == 0 && p.slab % SF_RANDAUG_PIX == 0;
+    hipLaunchKernelGGL(sf_randaug_hist_zero_kernel, dim3(N * T), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    if (check_launch("randaug_hist_zero")) return -1;
+    hipLaunchKernelGGL(sf_randaug_hist_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
+                       (hipStream_t)stream, p);
+    return check_launch("randaug_hist");
+}
+extern "C" int sf_randaug_layer_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
+                                   const int32_t* table_host, const int32_t* table_dev, const int32_t* hist, void* lut,
+                                   sf_stream_t stream) {
+    RandAugParams p;
+    if (fill_randaug_params("sf_randaug_layer_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
+    REQUIRE(dst && dst != src, "sf_randaug_layer_u8: dst must be another buffer than src");
+    int hist_rows, lut_rows;
+    if (check_randaug_table("sf_randaug_layer_u8", table_host, N, Hs, Ws, hist_rows, lut_rows)) return -1;
+    REQUIRE(hist_rows == 0 || hist, "sf_randaug_layer_u8: a row with AutoContrast, Equalize or Contrast needs the histograms");
+    REQUIRE(lut_rows == 0 || lut, "sf_randaug_layer_u8: a row with a table op needs the table scratch");
+    p.dst = (unsigned char*)dst; p.hist = const_cast<int32_t*>(hist); p.lut = (unsigned char*)lut;
+    p.vec = (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 && p.slab % SF_RANDAUG_PIX == 0;
+    if (lut_rows) {
+        hipLaunchKernelGGL(sf_randaug_lut_kernel, dim3(N * T), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+        if (check_launch("randaug_lut")) return -1;
+    }
+    hipLaunchKernelGGL(sf_randaug_stream_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
+                       (hipStream_t)stream, p);
+    return check_launch("randaug_stream");
 }
 
 static int row_scale_add_impl(const void* x, int32_t ldx, const float* scale, int64_t rows_per_sample, const void* resid,
