@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 29
+#define SF_ABI_VERSION 30
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -619,6 +619,31 @@ int sf_flat_adamw_tab(float* param, const float* grad, float* exp_avg, float* ex
 int sf_flat_lars_trust(const float* param, const float* grad, const void* segs, const int32_t* blk_seg, const int32_t* blk_off,
                        int32_t nblocks, const int32_t* seg_row, int32_t nseg, const float* ctl, const float* hyper, double* part,
                        float* trust, float clip_val, float trust_coef, float eps, sf_stream_t stream);
+
+/* MaskFeat step glue (ABI 30) -- the HOG regression targets of masked-feature pre-training (slowfast/models/operators.py:62-112,
+ * models/masked.py:254-281) in one launch, and the mask-token substitution after the patch embedding (masked.py:546-579).
+ * sf_hog_targets_f32: clip is the dense fp32 [B][3][T][H][W] clip; frames 0, ts, 2 ts, ... are used (Tu = ceil(T / ts)); cells
+ * are 8 x 8 pixels, 9 bins; fs = tokens per side of the target grid, u = (H / 8) / fs cells per token side.  out is fp32
+ * [B][Tu * fs * fs][27 * u * u]: token (t, i, j) is row (t * fs + i) * fs + j and feature ((c * 9 + bin) * u + dh) * u + dw is bin
+ * `bin` of colour channel c of cell (i * u + dh, j * u + dw).  Arithmetic: reflect-pad by 1; gx = (l0 - r0) + 2 (l1 - r1) + (l2 - r2)
+ * and gy likewise from the upper / lower neighbours, differences first (exact zeros on reflected borders and flat regions);
+ * norm = sqrt(gx^2 + gy^2); bin = floor(atan2(gx, gy) / pi * 9) mod 9 with gx == 0 in bin 0; per-cell sums of norm, divided by
+ * max(L2 norm over the 9 bins, 1e-12).  Fixed summation order (no atomics).  Rejected: H != W, H % (8 * fs) != 0, u > 17. */
+int sf_hog_targets_f32(const float* clip, int32_t B, int32_t T, int32_t H, int32_t W, int32_t ts, int32_t fs, float* out,
+                       sf_stream_t stream);
+/* x is the 16-bit token tensor [B][cls + T*H*W][C] (row pitch ldx) the patch embedding wrote (embed + bias + pos, cls row in
+ * front); mask the loader's uint8 window table [B][Tw][Hw][Ww] with Tw == T, H % Hw == 0, W % Ww == 0 (token (t, h, w) reads
+ * window (t, h / (H / Hw), w / (W / Ww))).  Forward, in place: every masked patch row becomes round16(mask_token + pos row)
+ * (pos: fp32 [cls + T*H*W][C] or NULL -> round16(mask_token)); other rows are not touched.  Backward: dx = dy with the masked rows
+ * zeroed; dpos (fp32 [cls + T*H*W][C] or NULL) = per-row sum over the batch of dy on masked rows, every row written; part is
+ * fp32 [sf_mask_tokens_bwd_blocks(cls + T*H*W, C)][2][C], whose slot-0 column sums are d(mask_token) (fold it with
+ * sf_colsum_finalize: fixed order, no atomics). */
+int sf_mask_tokens_fwd(void* x, int32_t ldx, int32_t B, int32_t cls, int32_t T, int32_t H, int32_t W, int32_t C, const void* mask,
+                       int32_t Tw, int32_t Hw, int32_t Ww, const float* mask_token, const float* pos, sf_stream_t stream);
+int sf_mask_tokens_bwd_blocks(int32_t rows, int32_t C);
+int sf_mask_tokens_bwd(const void* dy, int32_t lddy, void* dx, int32_t lddx, int32_t B, int32_t cls, int32_t T, int32_t H,
+                       int32_t W, int32_t C, const void* mask, int32_t Tw, int32_t Hw, int32_t Ww, float* dpos, float* part,
+                       sf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -130,7 +130,17 @@ _DEFAULTS = {
     "MIXUP": {"ENABLE": False, "ALPHA": 0.8, "CUTMIX_ALPHA": 1.0, "PROB": 1.0, "SWITCH_PROB": 0.5,
               "LABEL_SMOOTH_VALUE": 0.1},
     # slowfast/config/defaults.py:179-208 (the keys random_erasing.construct_random_erasing reads)
+    # (the mask keys of masked-feature pre-training -- GEN_MASK_LOADER, MASK_TUBE, MASK_FRAMES, MASK_WINDOW_SIZE, MASK_RATIO,
+    # MAX_MASK_PATCHES_PER_BLOCK, defaults.py:210-226 -- are not listed here: the key set of this section is pinned by
+    # tests/random_erasing_checks.py.  masking.AUG_MASK_DEFAULTS carries the reference's defaults for a cfg without them, and
+    # the MaskFeat preset below sets them.)
     "AUG": {"ENABLE": False, "RE_PROB": 0.25, "RE_MODE": "pixel", "RE_COUNT": 1, "RE_SPLIT": False},
+    # slowfast/config/defaults.py:563-609 (masked.MaskMViT)
+    "MASK": {"ENABLE": False, "MAE_ON": False, "MAE_RND_MASK": False, "PER_FRAME_MASKING": False, "TIME_STRIDE_LOSS": True,
+             "NORM_PRED_PIXEL": True, "SCALE_INIT_BY_DEPTH": False, "DECODER_EMBED_DIM": 512, "DECODER_SEP_POS_EMBED": False,
+             "DEC_KV_KERNEL": [], "DEC_KV_STRIDE": [], "PRETRAIN_DEPTH": [15], "HEAD_TYPE": "separate", "DECODER_DEPTH": 0,
+             "PRED_HOG": False},
+    "VIS_MASK": {"ENABLE": False},
     "NUM_GPUS": 1, "NUM_SHARDS": 1, "SHARD_ID": 0, "RNG_SEED": 1, "LOG_MODEL_INFO": True, "DIST_BACKEND": "nccl",
     "OUTPUT_DIR": ".",
 }
@@ -241,6 +251,26 @@ PRESETS["k400_VIT_B_16x4_FT"] = {
     "MODEL": {"NUM_CLASSES": 400, "ARCH": "mvit", "MODEL_NAME": "MViT", "LOSS_FUNC": "soft_cross_entropy",
               "DROPOUT_RATE": 0.3},
 }
+
+
+# configs/masked_ssl/k400_MVITv2_S_16x4_MaskFeat_PT.yaml (MaskFeat pre-training of MViTv2-S: no q pooling in block 14, a
+# 14 x 14 output grid, the dimension change after the Mlp as the yaml leaves DIM_MUL_IN_ATT at its default; HOG targets, cube
+# masks from the loader)
+PRESETS["MVITv2_S_16x4_MaskFeat_PT"] = copy.deepcopy(PRESETS["MVITv2_S_16x4"])
+PRESETS["MVITv2_S_16x4_MaskFeat_PT"]["MVIT"].update({
+    "POOL_Q_STRIDE": [[0, 1, 1, 1], [1, 1, 2, 2], [2, 1, 1, 1], [3, 1, 2, 2]] + [[i, 1, 1, 1] for i in range(4, 16)],
+    "DROPPATH_RATE": 0.0, "SEP_POS_EMBED": True, "DIM_MUL_IN_ATT": False})
+PRESETS["MVITv2_S_16x4_MaskFeat_PT"]["MASK"] = {"ENABLE": True, "PRETRAIN_DEPTH": [15], "HEAD_TYPE": "separate",
+                                                 "PRED_HOG": True}
+PRESETS["MVITv2_S_16x4_MaskFeat_PT"]["AUG"] = {"ENABLE": True, "RE_PROB": 0.0, "GEN_MASK_LOADER": True, "MASK_RATIO": 0.4,
+                                                "MASK_TUBE": False, "MASK_FRAMES": False, "MASK_WINDOW_SIZE": [8, 7, 7],
+                                                "MAX_MASK_PATCHES_PER_BLOCK": None}
+PRESETS["MVITv2_S_16x4_MaskFeat_PT"]["MIXUP"] = {"ENABLE": False}
+PRESETS["MVITv2_S_16x4_MaskFeat_PT"]["SOLVER"] = {"BASE_LR": 0.0001, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.05,
+                                                   "OPTIMIZING_METHOD": "adamw", "ZERO_WD_1D_PARAM": True,
+                                                   "CLIP_GRAD_L2NORM": 0.02}
+PRESETS["MVITv2_S_16x4_MaskFeat_PT"]["MODEL"] = {"NUM_CLASSES": 400, "ARCH": "maskmvit", "MODEL_NAME": "MaskMViT",
+                                                  "LOSS_FUNC": "multi_mse", "DROPOUT_RATE": 0.0}
 
 
 # configs/Kinetics/X3D_M.yaml

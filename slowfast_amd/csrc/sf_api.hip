@@ -21,6 +21,7 @@
 #include "sf_sample.h"
 #include "sf_color.h"
 #include "sf_randaug.h"
+#include "sf_hog.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -3206,4 +3207,83 @@ extern "C" int sf_flat_lars_trust(const float* param, const float* grad, const v
     if (check_launch("flat_lars_norms")) return -1;
     hipLaunchKernelGGL(sf_flat_lars_trust_kernel, dim3(nseg), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("flat_lars_trust");
+}
+
+// ================================================================================================
+// MaskFeat step glue (sf_hog.h, sf_tokens.h): HOG regression targets of the clip in one launch, mask-token substitution after
+// the patch embedding and its backward.  Kernel launches only.
+extern "C" int sf_hog_targets_f32(const float* clip, int32_t B, int32_t T, int32_t H, int32_t W, int32_t ts, int32_t fs,
+                                  float* out, sf_stream_t stream) {
+    REQUIRE(clip && out, "sf_hog_targets_f32: null pointer");
+    REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && ts > 0 && fs > 0, "sf_hog_targets_f32: bad shape");
+    REQUIRE(H == W, "sf_hog_targets_f32: H != W (%d x %d): the targets are defined for square clips", H, W);
+    REQUIRE(H % (SF_HOG_CELL * fs) == 0, "sf_hog_targets_f32: H %% (8 * fs) != 0 (H=%d, fs=%d): u = (H / 8) / fs must be a "
+            "whole number >= 1", H, fs);
+    HogParams p;
+    p.x = clip; p.out = out; p.T = T; p.H = H; p.W = W; p.ts = ts; p.Tu = (T + ts - 1) / ts; p.fs = fs;
+    p.u = H / SF_HOG_CELL / fs;
+    REQUIRE(p.u >= 1, "sf_hog_targets_f32: u < 1");
+    p.F = 3 * SF_HOG_BINS * p.u * p.u;
+    REQUIRE(SF_HOG_CELL * p.u <= SF_HOG_TILE_W && p.F <= SF_HOG_STAGE,
+            "sf_hog_targets_f32: u = %d cells per token side is beyond the built tile (u <= 17)", p.u);
+    int nj = SF_HOG_TILE_W / (SF_HOG_CELL * p.u);
+    if (nj > SF_HOG_STAGE / p.F) nj = SF_HOG_STAGE / p.F;
+    if (nj > fs) nj = fs;
+    p.nj = nj;
+    const int64_t gz = (int64_t)B * p.Tu;
+    REQUIRE(gz <= 65535 && fs <= 65535, "sf_hog_targets_f32: more than 65535 (sample, frame) pairs");
+    REQUIRE((int64_t)B * 3 * T * H * W < (1ll << 40), "sf_hog_targets_f32: clip too large");
+    const dim3 grid(cdiv(fs, nj), fs, (unsigned)gz);
+    if (nj * p.F <= SF_HOG_STAGE_SMALL)
+        hipLaunchKernelGGL(sf_hog_targets_kernel<SF_HOG_STAGE_SMALL>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(sf_hog_targets_kernel<SF_HOG_STAGE>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("hog_targets_f32");
+}
+
+static int fill_masktok(const char* who, MaskTokParams& p, int32_t B, int32_t cls, int32_t T, int32_t H, int32_t W, int32_t C,
+                        const void* mask, int32_t Tw, int32_t Hw, int32_t Ww) {
+    REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && C <= 2048 && (cls == 0 || cls == 1), "%s: bad shape", who);
+    REQUIRE(mask && Tw > 0 && Hw > 0 && Ww > 0, "%s: null mask table", who);
+    REQUIRE(Tw == T, "%s: the mask table has Tw = %d windows in time, the token grid T' = %d (Tw != T')", who, Tw, T);
+    REQUIRE(H % Hw == 0 && W % Ww == 0, "%s: the mask window grid %d x %d does not divide the token grid %d x %d", who, Hw, Ww,
+            H, W);
+    memset(&p, 0, sizeof(p));
+    p.mask = (const uint8_t*)mask; p.B = B; p.cls = cls; p.N = T * H * W; p.C = C;
+    p.H = H; p.W = W; p.Hw = Hw; p.Ww = Ww; p.rh = H / Hw; p.rw = W / Ww;
+    REQUIRE((int64_t)B * (p.N + cls) * (C / 8) < (1ll << 31), "%s: too many elements", who);
+    p.fdG = make_fastdiv((uint32_t)(C / 8)); p.fdN = make_fastdiv((uint32_t)p.N);
+    p.fdW = make_fastdiv((uint32_t)W); p.fdH = make_fastdiv((uint32_t)H);
+    p.groups = SF_THREADS / (C / 8);
+    return 0;
+}
+extern "C" int sf_mask_tokens_fwd(void* x, int32_t ldx, int32_t B, int32_t cls, int32_t T, int32_t H, int32_t W, int32_t C,
+                                  const void* mask, int32_t Tw, int32_t Hw, int32_t Ww, const float* mask_token,
+                                  const float* pos, sf_stream_t stream) {
+    MaskTokParams p;
+    if (fill_masktok("sf_mask_tokens_fwd", p, B, cls, T, H, W, C, mask, Tw, Hw, Ww)) return -1;
+    REQUIRE(x && mask_token && ldx >= C && ldx % 8 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)mask_token % 16 == 0 &&
+            (uintptr_t)pos % 16 == 0, "sf_mask_tokens_fwd: bad pointer / pitch");
+    p.x = (f16*)x; p.ldx = ldx; p.tok = mask_token; p.pos = pos;
+    p.total = (int64_t)B * p.N * (C / 8);
+    hipLaunchKernelGGL(sf_mask_tokens_fwd_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("mask_tokens_fwd");
+}
+extern "C" int sf_mask_tokens_bwd_blocks(int32_t rows, int32_t C) {
+    REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 2048, "sf_mask_tokens_bwd_blocks: bad shape");
+    const int groups = SF_THREADS / (C / 8);
+    return cdiv(rows, groups * SF_MASKTOK_RPT) * groups;
+}
+extern "C" int sf_mask_tokens_bwd(const void* dy, int32_t lddy, void* dx, int32_t lddx, int32_t B, int32_t cls, int32_t T,
+                                  int32_t H, int32_t W, int32_t C, const void* mask, int32_t Tw, int32_t Hw, int32_t Ww,
+                                  float* dpos, float* part, sf_stream_t stream) {
+    MaskTokParams p;
+    if (fill_masktok("sf_mask_tokens_bwd", p, B, cls, T, H, W, C, mask, Tw, Hw, Ww)) return -1;
+    REQUIRE(dy && dx && part && lddy >= C && lddy % 8 == 0 && lddx >= C && lddx % 8 == 0 && (uintptr_t)dy % 16 == 0 &&
+            (uintptr_t)dx % 16 == 0 && (uintptr_t)dpos % 16 == 0 && (uintptr_t)part % 16 == 0,
+            "sf_mask_tokens_bwd: bad pointer / pitch");
+    p.dy = (const f16*)dy; p.lddy = lddy; p.x = (f16*)dx; p.ldx = lddx; p.dpos = dpos; p.part = part;
+    const int blocks = cdiv(p.N + cls, p.groups * SF_MASKTOK_RPT);
+    hipLaunchKernelGGL(sf_mask_tokens_bwd_kernel, dim3(blocks), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("mask_tokens_bwd");
 }

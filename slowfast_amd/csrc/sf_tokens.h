@@ -785,3 +785,98 @@ __global__ __launch_bounds__(SF_THREADS) void sf_row_scale_add_kernel(RowScalePa
         st16(p.y + (int64_t)m * p.ldy + g8 * 8, o);
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// MaskFeat mask tokens (slowfast/models/masked.py:546-579): x = embed * (1 - m) + mask_token * m, then the cls row in front and
+// + pos_embed.  The patch embedding here already delivers act(embed + bias + pos) with the cls row in front, so the forward is
+// an in-place substitution of the masked patch rows by act(mask_token + pos_row) -- ONE rounding from fp32 operands (pos ==
+// nullptr: act(mask_token)); every other row, the cls row included, is not touched.  The mask is the loader's uint8 window
+// table (B, Tw, Hw, Ww), Tw == T: token (t, h, w) reads window (t, h / (H / Hw), w / (W / Ww)), which is
+// F.interpolate(mode="nearest") for the integer ratios the entry points require.
+//
+// Backward, one pass over dy + the column-sum finalize (two-stage, fixed order, no atomics):
+//   dx = dy with the masked rows zeroed (the patch convolution and its bias get nothing from them),
+//   d_pos[row][c] = sum over b of dy on masked rows (written for EVERY row: zeros where nothing is masked, the cls row too),
+//   part[(block, group)][0][c] = sum over the group's rows of d_pos: sf_colsum_finalize folds the table into d_mask_token.
+// A thread owns 8 channels of SF_MASKTOK_RPT consecutive rows and walks the batch in order.
+#define SF_MASKTOK_RPT 2
+struct MaskTokParams {
+    f16* x; int ldx;                // [B][cls + N][C] tokens (forward: in place; backward: dx)
+    const f16* dy; int lddy;
+    const uint8_t* mask;            // (B, T, Hw, Ww)
+    const float* tok;               // [C]
+    const float* pos;               // [cls + N][C] or nullptr
+    float* dpos;                    // [cls + N][C] or nullptr
+    float* part;                    // [gridDim.x * groups][2][C]
+    int B, cls, N, C;
+    int H, W, Hw, Ww, rh, rw;       // token grid, window grid, H / Hw, W / Ww
+    int groups;                     // row groups per block = SF_THREADS / (C / 8)
+    int64_t total;                  // forward: B * N * (C / 8)
+    FastDiv fdG, fdN, fdW, fdH;
+};
+__device__ __forceinline__ bool masktok_bit(const MaskTokParams& p, uint32_t b, uint32_t n) {
+    uint32_t r, w, t, h;
+    fd_divmod(n, p.fdW, r, w);
+    fd_divmod(r, p.fdH, t, h);
+    const uint32_t T = (uint32_t)p.N / (uint32_t)(p.H * p.W);
+    return p.mask[(((int64_t)b * T + t) * p.Hw + h / (uint32_t)p.rh) * p.Ww + w / (uint32_t)p.rw] != 0;
+}
+__global__ __launch_bounds__(SF_THREADS) void sf_mask_tokens_fwd_kernel(MaskTokParams p) {
+    for (int64_t idx = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x; idx < p.total; idx += (int64_t)gridDim.x * SF_THREADS) {
+        uint32_t q, g8, b, n;
+        fd_divmod((uint32_t)idx, p.fdG, q, g8);
+        fd_divmod(q, p.fdN, b, n);
+        if (!masktok_bit(p, b, n)) continue;
+        float v[8];
+        load8f(p.tok + g8 * 8, v);
+        if (p.pos) {
+            float pr[8];
+            load8f(p.pos + (int64_t)(p.cls + n) * p.C + g8 * 8, pr);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += pr[e];
+        }
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f16)v[e];
+        st16(p.x + ((int64_t)b * (p.cls + p.N) + p.cls + n) * p.ldx + g8 * 8, o);
+    }
+}
+__global__ __launch_bounds__(SF_THREADS) void sf_mask_tokens_bwd_kernel(MaskTokParams p) {
+    const int C8 = p.C / 8;
+    const int g = threadIdx.x / C8, c8 = threadIdx.x - g * C8;
+    if (g >= p.groups) return;
+    const int rows = p.cls + p.N;
+    const int m0 = ((int)blockIdx.x * p.groups + g) * SF_MASKTOK_RPT;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    for (int r = 0; r < SF_MASKTOK_RPT; ++r) {
+        const int m = m0 + r;
+        if (m >= rows) break;
+        float s[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = 0.f;
+        for (int b = 0; b < p.B; ++b) {
+            const int64_t row = (int64_t)b * rows + m;
+            f16x8 v = ld16(p.dy + row * p.lddy + c8 * 8);
+            if (m >= p.cls && masktok_bit(p, (uint32_t)b, (uint32_t)(m - p.cls))) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s[e] += (float)v[e];
+                v = zero8();
+            }
+            st16(p.x + row * p.ldx + c8 * 8, v);
+        }
+        if (p.dpos) {
+            float* d = p.dpos + (int64_t)m * p.C + c8 * 8;
+            *reinterpret_cast<f32x4*>(d) = (f32x4){s[0], s[1], s[2], s[3]};
+            *reinterpret_cast<f32x4*>(d + 4) = (f32x4){s[4], s[5], s[6], s[7]};
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += s[e];
+    }
+    float* d = p.part + ((int64_t)((int)blockIdx.x * p.groups + g) * 2) * p.C + c8 * 8;
+    *reinterpret_cast<f32x4*>(d) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
+    *reinterpret_cast<f32x4*>(d + 4) = (f32x4){acc[4], acc[5], acc[6], acc[7]};
+    *reinterpret_cast<f32x4*>(d + p.C) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4*>(d + p.C + 4) = (f32x4){0.f, 0.f, 0.f, 0.f};
+}

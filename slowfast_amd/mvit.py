@@ -405,16 +405,33 @@ class MViT(nn.Module):
                 names += ["cls_token"]
         return names
 
+    def _pos_embed(self):
+        """The [1, cls + THW, C] absolute position embedding (None without USE_ABS_POS): video_model_builder.py:1189-1203; tiny
+        parameter algebra."""
+        if not self.use_abs_pos:
+            return None
+        if self.sep_pos_embed:
+            pos = self.pos_embed_spatial.repeat(1, self.patch_dims[0], 1) + torch.repeat_interleave(
+                self.pos_embed_temporal, self.patch_dims[1] * self.patch_dims[2], dim=1)
+            if self.cls_embed_on:
+                pos = torch.cat([self.pos_embed_class, pos], 1)
+            return pos
+        return self.pos_embed
+
+    def _run_blocks(self, x, thw, side, collect=()):
+        """The block loop (shared with masked.MaskMViT): returns (x, thw, outputs of the blocks listed in ``collect``)."""
+        ncut = 4 if len(self.blocks) >= 8 else max(len(self.blocks) // 3, 1)      # MViTv2-S: [0-3 | 4-7 | 8-11 | 12-15 + head]
+        outs = []
+        for i, blk in enumerate(self.blocks):
+            if i and i % ncut == 0:                # backward segments of step.TrainStep (identity otherwise)
+                x = engine.cut(x)
+            x, thw = blk(x, thw, side)
+            if i in collect:
+                outs.append(x)
+        return x, thw, outs
+
     def forward(self, x, bboxes=None, return_attn=False):
-        pos = None
-        if self.use_abs_pos:                       # video_model_builder.py:1189-1203; tiny [1, N, C] parameter algebra
-            if self.sep_pos_embed:
-                pos = self.pos_embed_spatial.repeat(1, self.patch_dims[0], 1) + torch.repeat_interleave(
-                    self.pos_embed_temporal, self.patch_dims[1] * self.patch_dims[2], dim=1)
-                if self.cls_embed_on:
-                    pos = torch.cat([self.pos_embed_class, pos], 1)
-            else:
-                pos = self.pos_embed
+        pos = self._pos_embed()
         x, bcthw = self.patch_embed(x[0], self.cls_token if self.cls_embed_on else None, pos)
         T, H, W = bcthw[-3], bcthw[-2], bcthw[-1]
         assert (T, H, W) == (self.T, self.H, self.W), bcthw
@@ -422,12 +439,8 @@ class MViT(nn.Module):
         if self.enable_rev:                        # _forward_reversible, video_model_builder.py:1141-1164
             x = self.rev_backbone(x)               # fuse("concat") is the identity on the concatenated streams
         else:
-            ncut = 4 if len(self.blocks) >= 8 else max(len(self.blocks) // 3, 1)      # MViTv2-S: [0-3 | 4-7 | 8-11 | 12-15 + head]
             side = self._resid_side(x, pos)
-            for i, blk in enumerate(self.blocks):
-                if i and i % ncut == 0:                # backward segments of step.TrainStep (identity otherwise)
-                    x = engine.cut(x)
-                x, thw = blk(x, thw, side)
+            x, thw, _ = self._run_blocks(x, thw, side)
         if self.enable_detection:                  # video_model_builder.py:1218-1226
             x = TokenNormFn.apply(x, self, self.cls_embed_on, self.norm.weight, self.norm.bias)
             B, _, C = x.shape

@@ -54,7 +54,7 @@ def build_model(cfg, gpu_id=None, data_parallel=None):
         (flat gradient memory written in place by the backward kernels, HIP-graph replay -- what bench.py times)."""
     import os
 
-    from . import mvit, video_models, x3d  # noqa: F401  (registers the model classes)
+    from . import masked, mvit, video_models, x3d  # noqa: F401  (registers the model classes)
     if torch.cuda.is_available():
         assert cfg.NUM_GPUS <= torch.cuda.device_count(), "Cannot use more GPU devices than available"
     model = MODEL_REGISTRY.get(cfg.MODEL.MODEL_NAME)(cfg)

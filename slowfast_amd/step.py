@@ -92,11 +92,25 @@ class TrainStep:
             if record:
                 self._pack_plan = engine.WeightPackPlan(record)
 
+    def _loss_of(self, out, labels):
+        """(what .logits keeps, loss).  A model that returns ``(preds, labels)`` -- masked.MaskMViT, as tools/train_net.py does
+        under cfg.MASK.ENABLE -- brings its own labels (the ``labels`` argument of __call__ is a placeholder then), and a
+        tuple-valued loss (multi_mse: (sum, [losses])) contributes its first element."""
+        if isinstance(out, tuple):
+            preds, labels = out
+            loss = self.loss_fn([p.float() for p in preds], labels)
+            logits = preds[0]
+        else:
+            logits = out
+            loss = self.loss_fn(logits.float(), labels)
+        if isinstance(loss, (list, tuple)):
+            loss = loss[0]
+        return logits, loss
+
     def _fwd_bwd(self, inputs, labels):
         self.reducer.zero_grad()
         self._pack_weights()
-        logits = self.model(inputs)
-        loss = self.loss_fn(logits.float(), labels)
+        logits, loss = self._loss_of(self.model(inputs), labels)
         # FlatOptimizer: the (dynamic) loss scale is a device scalar -- a captured graph reads its current value at replay
         scale = self.optimizer.loss_scale if self._flat else self.loss_scale
         (loss * scale).backward()
@@ -112,10 +126,10 @@ class TrainStep:
         rec = engine._Segments()
         engine.SEGMENTS = rec
         try:
-            logits = self.model(inputs)
+            out = self.model(inputs)
         finally:
             engine.SEGMENTS = None
-        loss = self.loss_fn(logits.float(), labels)
+        logits, loss = self._loss_of(out, labels)
         scale = self.optimizer.loss_scale if self._flat else self.loss_scale
         return logits, loss, loss * scale, rec.cuts
 
@@ -228,6 +242,8 @@ class TrainStep:
         """The graph's own copy of an input: same strides (clone keeps a dense permuted layout), and the W-pair tag of a clip
         packed by data.pack_pathways_u8 travels with it -- engine.StemConvUnit must read the copy exactly as it would read the
         original, and a loader may later write packed clips straight into it (static_inputs())."""
+        if not torch.is_tensor(x):
+            return x                    # the meta slot of a [clip, meta, mask] input
         c = x.clone()
         if getattr(x, "_sf_wpairs", False):
             c._sf_wpairs = True
@@ -293,7 +309,7 @@ class TrainStep:
         else:
             pairs = zip(self._static_in, inputs) if self._is_list else [(self._static_in, inputs)]
             for dst, src in pairs:
-                if dst.data_ptr() != src.data_ptr():
+                if torch.is_tensor(dst) and dst.data_ptr() != src.data_ptr():
                     dst.copy_(src, non_blocking=True)
             if self._static_labels.data_ptr() != labels.data_ptr():
                 self._static_labels.copy_(labels, non_blocking=True)

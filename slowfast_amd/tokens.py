@@ -633,3 +633,73 @@ def transpose_heads(x, B, Nk, heads, D, ldk):
     _lib_call("sf_transpose_heads", x.data_ptr(), rows_pitch(x)[2], xt.data_ptr(), ldk, B, Nk, heads, D, _stream(x),
               work=dict(bytes=4.0 * x.numel()))
     return xt
+
+
+# ------------------------------------------------------------------------------------------------
+# MaskFeat mask tokens (csrc/sf_tokens.h: sf_mask_tokens_*; slowfast/models/masked.py:546-579)
+def _mask_table(mask, x, thw):
+    """Validated (Tw, Hw, Ww) of the loader's uint8 window table against the token grid."""
+    if not (torch.is_tensor(mask) and mask.dim() == 4 and mask.dtype == torch.uint8 and mask.is_contiguous()
+            and mask.device == x.device and mask.shape[0] == x.shape[0]):
+        raise SfError("mask tokens: the mask must be a dense uint8 (B, Tw, Hw, Ww) table on the tokens' device (got %s)" % (
+            "%s %s on %s" % (mask.dtype, tuple(mask.shape), mask.device) if torch.is_tensor(mask) else type(mask).__name__))
+    T, H, W = thw
+    Tw, Hw, Ww = (int(v) for v in mask.shape[1:])
+    if Tw != T:
+        raise SfError("mask tokens: the mask table has Tw = %d windows in time, the token grid T' = %d (Tw != T')" % (Tw, T))
+    if H % Hw or W % Ww:
+        raise SfError("mask tokens: the mask window grid %d x %d does not divide the token grid %d x %d" % (Hw, Ww, H, W))
+    return Tw, Hw, Ww
+
+
+def mask_tokens_fwd(x, mask, thw, mask_token, pos, cls):
+    """In place on the token tensor x [B, cls + T*H*W, C]: masked patch rows <- act(mask_token + pos row)."""
+    Tw, Hw, Ww = _mask_table(mask, x, thw)
+    B, N, C = x.shape
+    _, _, ld = rows_pitch(x)
+    assert N == int(cls) + thw[0] * thw[1] * thw[2] and mask_token.dtype == torch.float32 and mask_token.numel() == C
+    assert pos is None or (pos.dtype == torch.float32 and pos.is_contiguous() and pos.numel() == N * C)
+    _lib_call("sf_mask_tokens_fwd", x.data_ptr(), ld, B, int(cls), thw[0], thw[1], thw[2], C, mask.data_ptr(), Tw, Hw, Ww,
+              mask_token.data_ptr(), _ptr(pos), _stream(x), work=dict(bytes=2.0 * B * N * C))
+    return x
+
+
+def mask_tokens_bwd(dy, mask, thw, cls, want_dpos):
+    """(dx, d_mask_token [C] fp32, d_pos [cls + T*H*W, C] fp32 | None) from the gradient of the substituted tokens."""
+    Tw, Hw, Ww = _mask_table(mask, dy, thw)
+    B, N, C = dy.shape
+    _, _, lddy = rows_pitch(dy)
+    dx = torch.empty((B, N, C), dtype=_f16, device=dy.device)
+    dpos = torch.empty((N, C), dtype=torch.float32, device=dy.device) if want_dpos else None
+    dtok = torch.empty(C, dtype=torch.float32, device=dy.device)
+    nrows = _lib_call("sf_mask_tokens_bwd_blocks", N, C)
+    part = torch.empty((nrows, 2, C), dtype=torch.float32, device=dy.device)
+    _lib_call("sf_mask_tokens_bwd", dy.data_ptr(), lddy, dx.data_ptr(), C, B, int(cls), thw[0], thw[1], thw[2], C,
+              mask.data_ptr(), Tw, Hw, Ww, _ptr(dpos), part.data_ptr(), _stream(dy), work=dict(bytes=4.0 * B * N * C))
+    colsum_finalize(part, C, C, dtok, None, 1.0, False)
+    return dx, dtok, dpos
+
+
+class MaskTokenFn(torch.autograd.Function):
+    """x = embed * (1 - m) + mask_token * m (+ pos) on the output of the patch embedding, which already carries bias, position
+    embedding and the cls row: the masked patch rows are overwritten in place, their gradient goes to ``mask_token`` (and to
+    ``pos``) instead of the patch convolution."""
+
+    @staticmethod
+    def forward(ctx, x, mask, thw, cls, mask_token, pos):
+        tok = mask_token.detach().reshape(-1).float().contiguous()
+        p32 = pos.detach().reshape(-1, x.shape[-1]).float().contiguous() if pos is not None else None
+        mask_tokens_fwd(x, mask, thw, tok, p32, cls)
+        ctx.mark_dirty(x)
+        ctx.mask, ctx.thw, ctx.cls = mask, tuple(thw), cls
+        ctx.tok_shape, ctx.pos_shape = tuple(mask_token.shape), (tuple(pos.shape) if pos is not None else None)
+        return x
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy if dy.dtype == _f16 and dy.is_contiguous() else dy.to(_f16).contiguous()
+        want_dpos = ctx.pos_shape is not None and ctx.needs_input_grad[5]
+        dx, dtok, dpos = mask_tokens_bwd(dy, ctx.mask, ctx.thw, ctx.cls, want_dpos)
+        flush_finalizes()               # d_mask_token is handed to autograd now: a deferred fold must have been issued
+        return (dx, None, None, None, dtok.view(ctx.tok_shape) if ctx.needs_input_grad[4] else None,
+                dpos.view(ctx.pos_shape) if want_dpos else None)
