@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 30
+#define SF_ABI_VERSION 31
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -644,6 +644,41 @@ int sf_mask_tokens_bwd_blocks(int32_t rows, int32_t C);
 int sf_mask_tokens_bwd(const void* dy, int32_t lddy, void* dx, int32_t lddx, int32_t B, int32_t cls, int32_t T, int32_t H,
                        int32_t W, int32_t C, const void* mask, int32_t Tw, int32_t Hw, int32_t Ww, float* dpos, float* part,
                        sf_stream_t stream);
+
+/* MAE step glue (ABI 31) -- the kept-token gather in front of the encoder, the token assembly in front of the decoder
+ * (slowfast/models/masked.py:283-445) and the pixel regression targets (masked.py:178-230).
+ * ids is the int32 [B][L] ids_restore table, L = T'H'W' (the reference's argsort(argsort(noise))): patch row l of sample b is
+ * kept iff r = ids[b][l] < K (compared unsigned) and then lives at kept position r.  No entry of the table, whatever its
+ * value, makes a kernel read or write outside its buffers; a table that is not a permutation gives undefined values.
+ * Token tensors are 16-bit rows in the activation type with a row pitch (ld*, elements, % 8 == 0); C % 8 == 0, C <= 2048,
+ * cls in {0, 1}, 0 < K <= L.
+ * sf_token_keep_fwd: x [B][cls + L][C] (the patch embedding's output: bias, position embedding and cls row included) ->
+ * y [B][cls + K][C]: the cls row copied, source row l with r < K written to row cls + r.
+ * sf_token_keep_bwd: dx[b][cls + l] = r < K ? dy[b][cls + r] : 0, cls row copied; every row of dx [B][cls + L][C] is written.
+ * sf_token_restore_fwd: e [B][cls + K][C], mask_token fp32 [C], dpos fp32 [cls + L][C] ->
+ * y[b][cls + l] = round16((r < K ? e[b][cls + r] : mask_token) + dpos[cls + l]), y[b][0] = round16(e[b][0] + dpos[0]) with cls.
+ * sf_token_restore_bwd: one pass over dy [B][cls + L][C]: de[b][cls + r] = dy[b][cls + l] for kept rows (cls row copied);
+ * d_dpos (fp32 [cls + L][C] or NULL) = sum over the batch of dy, in batch order; part is fp32
+ * [sf_token_restore_bwd_blocks(cls + L, C)][2][C] whose slot-0 column sums are d(mask_token) (fold it with sf_colsum_finalize:
+ * fixed order, no atomics). */
+int sf_token_keep_fwd(const void* x, int32_t ldx, void* y, int32_t ldy, int32_t B, int32_t cls, int32_t L, int32_t K, int32_t C,
+                      const int32_t* ids, sf_stream_t stream);
+int sf_token_keep_bwd(const void* dy, int32_t lddy, void* dx, int32_t lddx, int32_t B, int32_t cls, int32_t L, int32_t K,
+                      int32_t C, const int32_t* ids, sf_stream_t stream);
+int sf_token_restore_fwd(const void* e, int32_t lde, void* y, int32_t ldy, int32_t B, int32_t cls, int32_t L, int32_t K,
+                         int32_t C, const int32_t* ids, const float* mask_token, const float* dpos, sf_stream_t stream);
+int sf_token_restore_bwd_blocks(int32_t rows, int32_t C);
+int sf_token_restore_bwd(const void* dy, int32_t lddy, void* de, int32_t ldde, int32_t B, int32_t cls, int32_t L, int32_t K,
+                         int32_t C, const int32_t* ids, float* d_dpos, float* part, sf_stream_t stream);
+/* sf_pixel_targets_f32: clip is the dense fp32 [B][3][T][H][W] clip, p the patch side, ts the temporal patch stride; u = 1 takes
+ * frames 0, ts, 2 ts, ... (MASK.TIME_STRIDE_LOSS), u = ts all frames.  out is fp32 [B][(T / ts) * (H / p) * (W / p)][u * p * p * 3]:
+ * token (t, i, j) is row (t * (H / p) + i) * (W / p) + j, feature ((uu * p + pp) * p + qq) * 3 + c is pixel (i * p + pp, j * p + qq)
+ * of channel c of frame t * ts + uu (the order of _patchify).  norm != 0: each row becomes (d - mean(d)) / sqrt(var(d) + 1e-6)
+ * with d_i = x_i - x_0 (shifted by the row's first element: a constant patch gives exact zeros), var unbiased; both sums in a
+ * fixed two-level order (64 lanes serially, then a 6-step fold).  Each used pixel is read once.  Rejected: H != W, H % p,
+ * T % ts, u not in {1, ts}, u * p * p * 3 > 8192. */
+int sf_pixel_targets_f32(const float* clip, int32_t B, int32_t T, int32_t H, int32_t W, int32_t ts, int32_t u, int32_t p,
+                         int32_t norm, float* out, sf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ from . import mvit  # noqa: F401,E402  (registers MViT)
 from . import x3d  # noqa: F401,E402  (registers X3D, the x3d_stem and x3d_transform factories)
 from . import masked  # noqa: F401,E402  (registers MaskMViT: MaskFeat pre-training with HOG targets)
 from .masking import MaskingGenerator, MaskingGenerator3D, construct_mask_generator  # noqa: F401,E402  (loader masks)
+from .masking import MaeMaskGenerator, construct_mae_mask_generator  # noqa: F401,E402  (MAE random masking: ids_restore tables)
 from .data import pack_pathways_u8  # noqa: F401,E402  (uint8 frames -> stem operand layout)
 from .mixup import MixUp, construct_mixup  # noqa: F401,E402  (MixUp / CutMix of the batch on the device)
 from .random_erasing import RandomErasing, ErasePlan, construct_random_erasing  # noqa: F401,E402  (random erasing on the device)

@@ -273,6 +273,25 @@ PRESETS["MVITv2_S_16x4_MaskFeat_PT"]["MODEL"] = {"NUM_CLASSES": 400, "ARCH": "ma
                                                   "LOSS_FUNC": "multi_mse", "DROPOUT_RATE": 0.0}
 
 
+# configs/masked_ssl/k400_VIT_B_16x4_MAE_PT.yaml (MAE pre-training of the plain video ViT-B: 90 % of the tokens removed by
+# random masking drawn per step, the encoder on the kept ones, a 4-block 512-wide decoder on all, normalised pixel targets)
+PRESETS["k400_VIT_B_16x4_MAE_PT"] = {
+    "DATA": {"NUM_FRAMES": 16, "SAMPLING_RATE": 4, "TRAIN_CROP_SIZE": 224, "TEST_CROP_SIZE": 224,
+             "INPUT_CHANNEL_NUM": [3]},
+    "MVIT": {"ZERO_DECAY_POS_CLS": False, "SEP_POS_EMBED": True, "PATCH_KERNEL": [2, 16, 16], "PATCH_STRIDE": [2, 16, 16],
+             "PATCH_PADDING": [0, 0, 0], "EMBED_DIM": 768, "NUM_HEADS": 12, "MLP_RATIO": 4.0, "QKV_BIAS": True,
+             "NORM": "layernorm", "DEPTH": 12, "DROPPATH_RATE": 0.0, "MODE": "conv", "CLS_EMBED_ON": True},
+    "MASK": {"ENABLE": True, "MAE_ON": True, "MAE_RND_MASK": True, "PRETRAIN_DEPTH": [11], "HEAD_TYPE": "separate_xformer",
+             "DECODER_DEPTH": 4, "DECODER_EMBED_DIM": 512},
+    "AUG": {"ENABLE": True, "RE_PROB": 0.0, "MASK_RATIO": 0.9},
+    "MIXUP": {"ENABLE": False},
+    "SOLVER": {"BASE_LR": 0.0001, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.05, "OPTIMIZING_METHOD": "adamw",
+               "ZERO_WD_1D_PARAM": True, "CLIP_GRAD_L2NORM": 0.02, "BETAS": [0.9, 0.95]},
+    "MODEL": {"NUM_CLASSES": 400, "ARCH": "maskmvit", "MODEL_NAME": "MaskMViT", "LOSS_FUNC": "multi_mse",
+              "DROPOUT_RATE": 0.0},
+}
+
+
 # configs/Kinetics/X3D_M.yaml
 PRESETS["X3D_M"] = {
     "DATA": {"NUM_FRAMES": 16, "SAMPLING_RATE": 5, "TRAIN_CROP_SIZE": 224, "TEST_CROP_SIZE": 256, "INPUT_CHANNEL_NUM": [3]},

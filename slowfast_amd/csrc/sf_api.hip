@@ -22,6 +22,7 @@
 #include "sf_color.h"
 #include "sf_randaug.h"
 #include "sf_hog.h"
+#include "sf_pixel.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -3286,4 +3287,93 @@ extern "C" int sf_mask_tokens_bwd(const void* dy, int32_t lddy, void* dx, int32_
     const int blocks = cdiv(p.N + cls, p.groups * SF_MASKTOK_RPT);
     hipLaunchKernelGGL(sf_mask_tokens_bwd_kernel, dim3(blocks), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("mask_tokens_bwd");
+}
+
+// ================================================================================================
+// MAE step glue (sf_tokens.h, sf_pixel.h): the encoder's kept-token gather, the decoder's token assembly, their backwards and
+// the pixel regression targets.  Kernel launches only.
+static int fill_tokids(const char* who, TokIdsParams& p, int32_t B, int32_t cls, int32_t L, int32_t K, int32_t C,
+                       const int32_t* ids) {
+    REQUIRE(B > 0 && L > 0 && C > 0 && C % 8 == 0 && C <= 2048 && (cls == 0 || cls == 1), "%s: bad shape", who);
+    REQUIRE(K > 0 && K <= L, "%s: K = %d kept tokens of L = %d (0 < K <= L)", who, K, L);
+    REQUIRE(ids && (uintptr_t)ids % 4 == 0, "%s: null ids_restore table", who);
+    memset(&p, 0, sizeof(p));
+    p.ids = ids; p.B = B; p.cls = cls; p.L = L; p.K = K; p.C = C;
+    p.total = (int64_t)B * (cls + L) * (C / 8);
+    REQUIRE(p.total < (1ll << 31), "%s: too many elements", who);
+    p.fdG = make_fastdiv((uint32_t)(C / 8)); p.fdN = make_fastdiv((uint32_t)(cls + L));
+    p.groups = SF_THREADS / (C / 8);
+    return 0;
+}
+static bool tok_rows_ok(const void* ptr, int32_t ld, int32_t C) { return ptr && ld >= C && ld % 8 == 0 && (uintptr_t)ptr % 16 == 0; }
+
+extern "C" int sf_token_keep_fwd(const void* x, int32_t ldx, void* y, int32_t ldy, int32_t B, int32_t cls, int32_t L, int32_t K,
+                                 int32_t C, const int32_t* ids, sf_stream_t stream) {
+    TokIdsParams p;
+    if (fill_tokids("sf_token_keep_fwd", p, B, cls, L, K, C, ids)) return -1;
+    REQUIRE(tok_rows_ok(x, ldx, C) && tok_rows_ok(y, ldy, C), "sf_token_keep_fwd: bad pointer / pitch");
+    p.x = (const f16*)x; p.ldx = ldx; p.y = (f16*)y; p.ldy = ldy;
+    hipLaunchKernelGGL(sf_token_keep_fwd_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("token_keep_fwd");
+}
+extern "C" int sf_token_keep_bwd(const void* dy, int32_t lddy, void* dx, int32_t lddx, int32_t B, int32_t cls, int32_t L,
+                                 int32_t K, int32_t C, const int32_t* ids, sf_stream_t stream) {
+    TokIdsParams p;
+    if (fill_tokids("sf_token_keep_bwd", p, B, cls, L, K, C, ids)) return -1;
+    REQUIRE(tok_rows_ok(dy, lddy, C) && tok_rows_ok(dx, lddx, C), "sf_token_keep_bwd: bad pointer / pitch");
+    p.x = (const f16*)dy; p.ldx = lddy; p.y = (f16*)dx; p.ldy = lddx;
+    hipLaunchKernelGGL(sf_token_keep_bwd_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("token_keep_bwd");
+}
+extern "C" int sf_token_restore_fwd(const void* e, int32_t lde, void* y, int32_t ldy, int32_t B, int32_t cls, int32_t L,
+                                    int32_t K, int32_t C, const int32_t* ids, const float* mask_token, const float* dpos,
+                                    sf_stream_t stream) {
+    TokIdsParams p;
+    if (fill_tokids("sf_token_restore_fwd", p, B, cls, L, K, C, ids)) return -1;
+    REQUIRE(tok_rows_ok(e, lde, C) && tok_rows_ok(y, ldy, C) && mask_token && dpos && (uintptr_t)mask_token % 16 == 0 &&
+            (uintptr_t)dpos % 16 == 0, "sf_token_restore_fwd: bad pointer / pitch");
+    p.x = (const f16*)e; p.ldx = lde; p.y = (f16*)y; p.ldy = ldy; p.tok = mask_token; p.pos = dpos;
+    hipLaunchKernelGGL(sf_token_restore_fwd_kernel, dim3(pool_grid(p.total)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("token_restore_fwd");
+}
+extern "C" int sf_token_restore_bwd_blocks(int32_t rows, int32_t C) {
+    REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 2048, "sf_token_restore_bwd_blocks: bad shape");
+    const int groups = SF_THREADS / (C / 8);
+    return cdiv(rows, groups * SF_TOKRESTORE_RPT) * groups;
+}
+extern "C" int sf_token_restore_bwd(const void* dy, int32_t lddy, void* de, int32_t ldde, int32_t B, int32_t cls, int32_t L,
+                                    int32_t K, int32_t C, const int32_t* ids, float* d_dpos, float* part, sf_stream_t stream) {
+    TokIdsParams p;
+    if (fill_tokids("sf_token_restore_bwd", p, B, cls, L, K, C, ids)) return -1;
+    REQUIRE(tok_rows_ok(dy, lddy, C) && tok_rows_ok(de, ldde, C) && part && (uintptr_t)part % 16 == 0 &&
+            (uintptr_t)d_dpos % 16 == 0, "sf_token_restore_bwd: bad pointer / pitch");
+    p.x = (const f16*)dy; p.ldx = lddy; p.y = (f16*)de; p.ldy = ldde; p.dpos = d_dpos; p.part = part;
+    const int blocks = cdiv(cls + L, p.groups * SF_TOKRESTORE_RPT);
+    hipLaunchKernelGGL(sf_token_restore_bwd_kernel, dim3(blocks), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("token_restore_bwd");
+}
+
+extern "C" int sf_pixel_targets_f32(const float* clip, int32_t B, int32_t T, int32_t H, int32_t W, int32_t ts, int32_t u,
+                                    int32_t p_, int32_t norm, float* out, sf_stream_t stream) {
+    REQUIRE(clip && out, "sf_pixel_targets_f32: null pointer");
+    REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && ts > 0 && u > 0 && p_ > 0, "sf_pixel_targets_f32: bad shape");
+    REQUIRE(H == W, "sf_pixel_targets_f32: H != W (%d x %d): the targets are defined for square clips", H, W);
+    REQUIRE(H % p_ == 0, "sf_pixel_targets_f32: H %% p != 0 (H=%d, p=%d)", H, p_);
+    REQUIRE(T % ts == 0, "sf_pixel_targets_f32: T %% ts != 0 (T=%d, ts=%d)", T, ts);
+    REQUIRE(u == 1 || u == ts, "sf_pixel_targets_f32: u = %d frames per token: u must be 1 (TIME_STRIDE_LOSS) or ts = %d", u, ts);
+    const int64_t n = (int64_t)u * p_ * p_ * 3;
+    REQUIRE(n <= SF_PIXEL_STAGE, "sf_pixel_targets_f32: a row of u * p * p * 3 = %lld values is beyond the staged row (<= %d)",
+            (long long)n, SF_PIXEL_STAGE);
+    PixelParams p;
+    p.x = clip; p.out = out; p.T = T; p.H = H; p.W = W; p.ts = ts; p.Tt = T / ts; p.u = u; p.p = p_;
+    p.h = H / p_; p.w = W / p_; p.n = (int)n; p.norm = norm ? 1 : 0;
+    const int njmax = SF_PIXEL_STAGE / p.n < p.w ? SF_PIXEL_STAGE / p.n : p.w;
+    const int chunks = cdiv(p.w, njmax);
+    p.nj = cdiv(p.w, chunks);                              // balanced chunks: 14 tokens of 768 values -> 7 + 7
+    p.fdRun = make_fastdiv((uint32_t)(p.nj * p_)); p.fdP = make_fastdiv((uint32_t)p_); p.fdUP = make_fastdiv((uint32_t)(u * p_));
+    const int64_t gz = (int64_t)B * p.Tt;
+    REQUIRE(gz <= 65535 && p.h <= 65535, "sf_pixel_targets_f32: more than 65535 (sample, token frame) pairs");
+    REQUIRE((int64_t)B * 3 * T * H * W < (1ll << 40), "sf_pixel_targets_f32: clip too large");
+    hipLaunchKernelGGL(sf_pixel_targets_kernel, dim3(chunks, p.h, (unsigned)gz), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("pixel_targets_f32");
 }

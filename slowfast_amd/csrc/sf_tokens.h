@@ -880,3 +880,128 @@ __global__ __launch_bounds__(SF_THREADS) void sf_mask_tokens_bwd_kernel(MaskTokP
     *reinterpret_cast<f32x4*>(d + p.C) = (f32x4){0.f, 0.f, 0.f, 0.f};
     *reinterpret_cast<f32x4*>(d + p.C + 4) = (f32x4){0.f, 0.f, 0.f, 0.f};
 }
+
+// ------------------------------------------------------------------------------------------------
+// MAE token glue (slowfast/models/masked.py:283-445): the encoder runs on the KEPT tokens only, the decoder on all of them.
+// One table drives the four kernels: ids_restore, int32 [B][L] -- the reference's argsort(argsort(noise)).  Patch row l of
+// sample b is kept iff r = ids_restore[b][l] < K, and then lives at kept position r.  r is compared UNSIGNED against K, so a
+// negative or oversized entry is simply "not kept": whatever the table holds, no access leaves the buffers (a table that is
+// not a permutation gives undefined values -- two rows may claim one kept slot, a slot may stay unwritten -- nothing more).
+//
+//   keep fwd      y[b][cls + r] = x[b][cls + l] for kept rows, the cls row copied: x is the patch embedding's output, which
+//                 already carries bias + position embedding, so this IS gather(x) + gather(pos_embed) with one rounding.
+//   keep bwd      dx[b][cls + l] = kept ? dy[b][cls + r] : 0 -- EVERY row of dx is written.
+//   restore fwd   y[b][cls + l] = act((kept ? e[b][cls + r] : mask_token) + dpos[cls + l]), y[b][0] = act(e[b][0] + dpos[0]):
+//                 cat / repeat / gather / += of the reference in one pass, one rounding from fp32.
+//   restore bwd   one pass over dy (the two-stage shape of sf_mask_tokens_bwd): de[b][cls + r] = dy[b][cls + l] for kept
+//                 rows (cls row copied), d_dpos[row] = sum over b of dy[b][row] in batch order, and per (block, group) the
+//                 sum over the group's rows of the masked rows' dy: part[..][0][c], folded into d_mask_token by
+//                 sf_colsum_finalize.  Fixed order, no atomics.
+struct TokIdsParams {
+    const f16* x; int ldx;          // source rows (keep fwd: [B][cls + L][C]; keep bwd / restore fwd: [B][cls + K][C])
+    f16* y; int ldy;                // destination rows
+    const int32_t* ids;             // [B][L]
+    const float* tok;               // restore: mask_token [C]
+    const float* pos;               // restore: decoder position table [cls + L][C]
+    float* dpos;                    // restore bwd: [cls + L][C] or nullptr
+    float* part;                    // restore bwd: [gridDim.x * groups][2][C]
+    int B, cls, L, K, C;
+    int groups;                     // restore bwd: row groups per block = SF_THREADS / (C / 8)
+    int64_t total;                  // elementwise kernels: B * (cls + L) * (C / 8)
+    FastDiv fdG, fdN;               // C / 8, cls + L
+};
+// (b, m, g8) of a flat index over [B][cls + L][C / 8] and whether row m is kept (r: its kept position); the cls row counts as
+// kept at position -cls, i.e. row 0 of the short tensor
+__device__ __forceinline__ bool tokids_item(const TokIdsParams& p, int64_t idx, uint32_t& b, uint32_t& m, uint32_t& g8,
+                                            uint32_t& srow) {
+    uint32_t q;
+    fd_divmod((uint32_t)idx, p.fdG, q, g8);
+    fd_divmod(q, p.fdN, b, m);
+    if (m < (uint32_t)p.cls) { srow = m; return true; }
+    const uint32_t r = (uint32_t)p.ids[(int64_t)b * p.L + (m - p.cls)];
+    srow = (uint32_t)p.cls + r;
+    return r < (uint32_t)p.K;
+}
+__global__ __launch_bounds__(SF_THREADS) void sf_token_keep_fwd_kernel(TokIdsParams p) {
+    for (int64_t idx = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x; idx < p.total; idx += (int64_t)gridDim.x * SF_THREADS) {
+        uint32_t b, m, g8, srow;
+        if (!tokids_item(p, idx, b, m, g8, srow)) continue;
+        st16(p.y + ((int64_t)b * (p.cls + p.K) + srow) * p.ldy + g8 * 8,
+             ld16(p.x + ((int64_t)b * (p.cls + p.L) + m) * p.ldx + g8 * 8));
+    }
+}
+__global__ __launch_bounds__(SF_THREADS) void sf_token_keep_bwd_kernel(TokIdsParams p) {
+    for (int64_t idx = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x; idx < p.total; idx += (int64_t)gridDim.x * SF_THREADS) {
+        uint32_t b, m, g8, srow;
+        const bool kept = tokids_item(p, idx, b, m, g8, srow);
+        const f16x8 v = kept ? ld16(p.x + ((int64_t)b * (p.cls + p.K) + srow) * p.ldx + g8 * 8) : zero8();
+        st16(p.y + ((int64_t)b * (p.cls + p.L) + m) * p.ldy + g8 * 8, v);
+    }
+}
+__global__ __launch_bounds__(SF_THREADS) void sf_token_restore_fwd_kernel(TokIdsParams p) {
+    for (int64_t idx = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x; idx < p.total; idx += (int64_t)gridDim.x * SF_THREADS) {
+        uint32_t b, m, g8, srow;
+        const bool kept = tokids_item(p, idx, b, m, g8, srow);
+        float v[8], pr[8];
+        if (kept) {
+            const f16x8 e = ld16(p.x + ((int64_t)b * (p.cls + p.K) + srow) * p.ldx + g8 * 8);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = (float)e[k];
+        } else {
+            load8f(p.tok + g8 * 8, v);
+        }
+        load8f(p.pos + (int64_t)m * p.C + g8 * 8, pr);
+        f16x8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = (f16)(v[k] + pr[k]);
+        st16(p.y + ((int64_t)b * (p.cls + p.L) + m) * p.ldy + g8 * 8, o);
+    }
+}
+#define SF_TOKRESTORE_RPT 2
+__global__ __launch_bounds__(SF_THREADS) void sf_token_restore_bwd_kernel(TokIdsParams p) {
+    const int C8 = p.C / 8;
+    const int g = threadIdx.x / C8, c8 = threadIdx.x - g * C8;
+    if (g >= p.groups) return;
+    const int rows = p.cls + p.L, krows = p.cls + p.K;
+    const int m0 = ((int)blockIdx.x * p.groups + g) * SF_TOKRESTORE_RPT;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    for (int r = 0; r < SF_TOKRESTORE_RPT; ++r) {
+        const int m = m0 + r;
+        if (m >= rows) break;
+        float s[8], t[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { s[e] = 0.f; t[e] = 0.f; }
+        for (int b = 0; b < p.B; ++b) {
+            const f16x8 v = ld16(p.x + ((int64_t)b * rows + m) * p.ldx + c8 * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += (float)v[e];
+            uint32_t kr = (uint32_t)m;                      // the cls row is row 0 of de
+            bool kept = true;
+            if (m >= p.cls) {
+                kr = (uint32_t)p.ids[(int64_t)b * p.L + (m - p.cls)];
+                kept = kr < (uint32_t)p.K;
+                kr += (uint32_t)p.cls;
+            }
+            if (kept) {
+                st16(p.y + ((int64_t)b * krows + kr) * p.ldy + c8 * 8, v);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) t[e] += (float)v[e];
+            }
+        }
+        if (p.dpos) {
+            float* d = p.dpos + (int64_t)m * p.C + c8 * 8;
+            *reinterpret_cast<f32x4*>(d) = (f32x4){s[0], s[1], s[2], s[3]};
+            *reinterpret_cast<f32x4*>(d + 4) = (f32x4){s[4], s[5], s[6], s[7]};
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += t[e];
+    }
+    float* d = p.part + ((int64_t)((int)blockIdx.x * p.groups + g) * 2) * p.C + c8 * 8;
+    *reinterpret_cast<f32x4*>(d) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
+    *reinterpret_cast<f32x4*>(d + 4) = (f32x4){acc[4], acc[5], acc[6], acc[7]};
+    *reinterpret_cast<f32x4*>(d + p.C) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4*>(d + p.C + 4) = (f32x4){0.f, 0.f, 0.f, 0.f};
+}

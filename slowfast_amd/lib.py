@@ -11,7 +11,7 @@ import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 30
+ABI_VERSION = 31
 # 16-bit storage type of activations / packed weights / MFMA operands, fixed per PROCESS: SF_ACT_DTYPE=fp16 (default) loads
 # libsfamd.so, =bf16 loads libsfamd_bf16.so -- the same sources compiled with -DSF_ACT_BF16 (bfloat16 storage,
 # v_mfma_f32_16x16x32_bf16); both are what torch.cuda.amp.autocast admits on the reference side (tools/train_net.py:101-118).
@@ -200,6 +200,12 @@ _SIGNATURES = {
     "sf_mask_tokens_bwd_blocks": (c_int, [c_int32, c_int32]),
     "sf_mask_tokens_bwd": (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32,
                                    c_int32, c_int32, _F, _F, _P]),
+    "sf_token_keep_fwd": (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "sf_token_keep_bwd": (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "sf_token_restore_fwd": (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _F, _F, _P]),
+    "sf_token_restore_bwd_blocks": (c_int, [c_int32, c_int32]),
+    "sf_token_restore_bwd": (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _F, _F, _P]),
+    "sf_pixel_targets_f32": (c_int, [_F, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _F, _P]),
     "sf_row_scale_add": (c_int, [_P, c_int32, _P, c_int64, _P, c_int32, _P, c_int32, c_int64, c_int32, _P]),
     "sf_row_scale_add_rows32": (c_int, [_P, c_int32, _P, c_int64, _P, c_int32, _P, c_int32, c_int64, c_int32,
                                         POINTER(Rows32), _P]),

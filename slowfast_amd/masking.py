@@ -151,6 +151,38 @@ class MaskSampler:
         return torch.from_numpy(np.stack([self() for _ in range(n)]).astype(np.uint8))
 
 
+class MaeMaskGenerator:
+    """The random masking of MAE (slowfast/models/masked.py:283-317, MASK.MAE_RND_MASK) drawn on the host:
+    ``sample_batch(N)`` is the int32 ``(N, L)`` ids_restore table -- argsort(argsort(noise)) of ``torch.rand(N, L)`` on torch's
+    CPU generator, so a loop seeded with ``torch.manual_seed`` like a CPU run of the reference keeps and removes the same
+    tokens.  Row l of sample b is kept iff ``ids_restore[b][l] < len_keep``.  (A stable sort: equal noise values, which the
+    reference orders as its sort happens to, keep their order here.)"""
+
+    def __init__(self, num_tokens, mask_ratio):
+        self.num_tokens, self.mask_ratio = int(num_tokens), float(mask_ratio)
+        self.len_keep = int(self.num_tokens * (1 - self.mask_ratio))       # the reference's expression: 64 * (1 - 0.9) -> 6
+        assert self.len_keep > 1
+
+    def sample_batch(self, n):
+        noise = torch.rand(n, self.num_tokens)
+        ids_shuffle = torch.argsort(noise, dim=1, stable=True)
+        return torch.argsort(ids_shuffle, dim=1, stable=True).to(torch.int32)
+
+    def mask(self, ids_restore):
+        """The reference's binary mask of a table: 1.0 on removed rows."""
+        return (ids_restore >= self.len_keep).float()
+
+
+def construct_mae_mask_generator(cfg):
+    """The ids_restore source of a cfg with MASK.MAE_ON and MASK.MAE_RND_MASK (None otherwise)."""
+    if not (cfg.MASK.MAE_ON and cfg.MASK.MAE_RND_MASK):
+        return None
+    stride = cfg.MVIT.PATCH_STRIDE
+    tokens = ((cfg.DATA.NUM_FRAMES // stride[0]) * (cfg.DATA.TRAIN_CROP_SIZE // stride[1])
+              * (cfg.DATA.TRAIN_CROP_SIZE // stride[2]))
+    return MaeMaskGenerator(tokens, _aug(cfg, "MASK_RATIO"))
+
+
 def construct_mask_generator(cfg):
     """The mask source of a cfg with AUG.GEN_MASK_LOADER (None otherwise)."""
     if not _aug(cfg, "GEN_MASK_LOADER"):

@@ -703,3 +703,116 @@ class MaskTokenFn(torch.autograd.Function):
         flush_finalizes()               # d_mask_token is handed to autograd now: a deferred fold must have been issued
         return (dx, None, None, None, dtok.view(ctx.tok_shape) if ctx.needs_input_grad[4] else None,
                 dpos.view(ctx.pos_shape) if want_dpos else None)
+
+
+# ------------------------------------------------------------------------------------------------
+# MAE token glue (csrc/sf_tokens.h: sf_token_keep_* / sf_token_restore_*; slowfast/models/masked.py:283-445)
+def _ids_table(ids, x, L):
+    """The validated int32 (B, L) ids_restore table of a token tensor x [B, ., C]."""
+    if not (torch.is_tensor(ids) and ids.dim() == 2 and ids.dtype == torch.int32 and ids.is_contiguous()
+            and ids.device == x.device and tuple(ids.shape) == (x.shape[0], L)):
+        raise SfError("MAE tokens: ids_restore must be a dense int32 (B, L) = (%d, %d) table on the tokens' device (got %s)" % (
+            x.shape[0], L, "%s %s on %s" % (ids.dtype, tuple(ids.shape), ids.device) if torch.is_tensor(ids)
+            else type(ids).__name__))
+    return ids
+
+
+def _tok3(x, what):
+    if not (torch.is_tensor(x) and x.dim() == 3):
+        raise SfError("%s: expected a [B, N, C] token tensor" % what)
+    _, C, ld = rows_pitch(x)
+    return int(x.shape[0]), int(x.shape[1]), C, ld
+
+
+def token_keep_fwd(x, ids, K, cls):
+    """x [B, cls + L, C] -> [B, cls + K, C]: the cls row and the rows l with ids[b][l] < K, at position cls + ids[b][l]."""
+    B, N, C, ldx = _tok3(x, "token_keep_fwd")
+    L, K, cls = N - int(cls), int(K), int(cls)
+    _ids_table(ids, x, L)
+    y = torch.empty((B, cls + K, C), dtype=_f16, device=x.device)
+    _lib_call("sf_token_keep_fwd", x.data_ptr(), ldx, y.data_ptr(), C, B, cls, L, K, C, ids.data_ptr(), _stream(x),
+              work=dict(bytes=4.0 * B * (cls + K) * C + 4.0 * B * L))
+    return y
+
+
+def token_keep_bwd(dy, ids, L, cls):
+    """dy [B, cls + K, C] -> dx [B, cls + L, C]: kept rows from their kept position, zeros elsewhere (every row written)."""
+    B, Nk, C, lddy = _tok3(dy, "token_keep_bwd")
+    L, cls = int(L), int(cls)
+    _ids_table(ids, dy, L)
+    dx = torch.empty((B, cls + L, C), dtype=_f16, device=dy.device)
+    _lib_call("sf_token_keep_bwd", dy.data_ptr(), lddy, dx.data_ptr(), C, B, cls, L, Nk - cls, C, ids.data_ptr(), _stream(dy),
+              work=dict(bytes=2.0 * B * (Nk + cls + L) * C + 4.0 * B * L))
+    return dx
+
+
+def token_restore_fwd(e, ids, mask_token, dpos, cls):
+    """e [B, cls + K, C], mask_token fp32 [C], dpos fp32 [cls + L, C] -> y [B, cls + L, C] =
+    act((kept ? e row : mask_token) + dpos row), one rounding."""
+    B, Nk, C, lde = _tok3(e, "token_restore_fwd")
+    cls = int(cls)
+    L = int(dpos.shape[0]) - cls
+    _ids_table(ids, e, L)
+    assert mask_token.dtype == torch.float32 and mask_token.numel() == C and mask_token.is_contiguous()
+    assert dpos.dtype == torch.float32 and dpos.is_contiguous() and tuple(dpos.shape) == (cls + L, C)
+    y = torch.empty((B, cls + L, C), dtype=_f16, device=e.device)
+    _lib_call("sf_token_restore_fwd", e.data_ptr(), lde, y.data_ptr(), C, B, cls, L, Nk - cls, C, ids.data_ptr(),
+              mask_token.data_ptr(), dpos.data_ptr(), _stream(e),
+              work=dict(bytes=2.0 * B * (Nk + cls + L) * C + 4.0 * (cls + L) * C + 4.0 * B * L))
+    return y
+
+
+def token_restore_bwd(dy, ids, K, cls, want_dpos=True):
+    """(de [B, cls + K, C], d_mask_token [C] fp32, d_dpos [cls + L, C] fp32 | None) from dy [B, cls + L, C]."""
+    B, N, C, lddy = _tok3(dy, "token_restore_bwd")
+    K, cls = int(K), int(cls)
+    L = N - cls
+    _ids_table(ids, dy, L)
+    de = torch.empty((B, cls + K, C), dtype=_f16, device=dy.device)
+    ddpos = torch.empty((N, C), dtype=torch.float32, device=dy.device) if want_dpos else None
+    dtok = torch.empty(C, dtype=torch.float32, device=dy.device)
+    nrows = _lib_call("sf_token_restore_bwd_blocks", N, C)
+    part = torch.empty((nrows, 2, C), dtype=torch.float32, device=dy.device)
+    _lib_call("sf_token_restore_bwd", dy.data_ptr(), lddy, de.data_ptr(), C, B, cls, L, K, C, ids.data_ptr(), _ptr(ddpos),
+              part.data_ptr(), _stream(dy), work=dict(bytes=2.0 * B * (N + cls + K) * C + 4.0 * N * C + 4.0 * B * L))
+    colsum_finalize(part, C, C, dtok, None, 1.0, False)
+    return de, dtok, ddpos
+
+
+class TokenKeepFn(torch.autograd.Function):
+    """The encoder input of MAE: the kept rows of the patch embedding's output (which already carries bias, position embedding
+    and the cls row) at their kept positions.  The backward writes every row of dx (zeros on dropped rows), so the patch
+    convolution and the position embedding see the reference's gradients."""
+
+    @staticmethod
+    def forward(ctx, x, ids, K, cls):
+        ctx.ids, ctx.L, ctx.cls = ids, x.shape[1] - int(cls), int(cls)
+        return token_keep_fwd(x, ids, K, cls)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy if dy.dtype == _f16 else dy.to(_f16)
+        return token_keep_bwd(dy.contiguous(), ctx.ids, ctx.L, ctx.cls), None, None, None
+
+
+class TokenRestoreFn(torch.autograd.Function):
+    """The decoder input of MAE from the decoder embedding of the kept rows: mask tokens on the dropped rows, the original
+    order, + the decoder position embedding -- cat / repeat / gather / += of the reference in one launch.  ``dpos`` is the
+    [1, cls + L, C] decoder position table (a parameter or the sum of the separate tables)."""
+
+    @staticmethod
+    def forward(ctx, e, ids, cls, mask_token, dpos):
+        C = e.shape[-1]
+        tok = mask_token.detach().reshape(-1).float().contiguous()
+        p32 = dpos.detach().reshape(-1, C).float().contiguous()
+        ctx.ids, ctx.K, ctx.cls = ids, e.shape[1] - int(cls), int(cls)
+        ctx.tok_shape, ctx.pos_shape = tuple(mask_token.shape), tuple(dpos.shape)
+        return token_restore_fwd(e, ids, tok, p32, cls)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy if dy.dtype == _f16 else dy.to(_f16)
+        de, dtok, ddpos = token_restore_bwd(dy.contiguous(), ctx.ids, ctx.K, ctx.cls, want_dpos=ctx.needs_input_grad[4])
+        flush_finalizes()               # d_mask_token is handed to autograd now: a deferred fold must have been issued
+        return (de, None, None, dtok.view(ctx.tok_shape) if ctx.needs_input_grad[3] else None,
+                ddpos.view(ctx.pos_shape) if ctx.needs_input_grad[4] else None)
