@@ -52,7 +52,7 @@ class GradReducer:
         self._prescale, self._prescaled = 1.0 / self.world, set()   # compressed buckets are averaged before the cast
         def listener(params):
             self._on_ready(params)
-        # weight gradients / the other pathway's gradients may still be running on a side stream when a block announces its
+        # the other pathway's / branch's gradients may still be running on their own stream when a block announces its
         # parameters.  The join (engine.join_side_streams) is made where a collective is actually launched (_launch: a bucket
         # is complete), not on every announcement -- joining per block serialised the Slow and Fast pathways' backward in the
         # eager multi-GPU path

@@ -8,11 +8,11 @@ from the raw conv outputs it saved).  Autograd only chains blocks.
 Fusion plan per bottleneck block (reference graph: slowfast/models/resnet_helper.py:377-392, :512-521):
 
     forward   ya = conv_a(x)            [+ per-channel sum/sumsq in the epilogue]
-              yb = conv_b(relu(bn_a(ya)))    BN+ReLU of `a` applied while loading conv_b's operand
+              yb = conv_b(relu(bn_a(ya)))    BN+ReLU of `a` written once in fp16 (one elementwise pass)
               yc = conv_c(relu(bn_b(yb)))
               out = relu(bn_c(yc) + shortcut)      shortcut = x | bn_1(conv_1(x)), one elementwise pass
     backward  (dyc[, dy1|g]) <- BN backward of dout masked by (out > 0)
-              wgrad_c / dgrad_c with relu(bn_b(yb)) recomputed on the fly, ... down to
+              wgrad_c / dgrad_c on the saved relu(bn_b(yb)), ... down to
               dx = dgrad_a(dya) + (g | dgrad_1(dy1))      residual add fused in the dgrad epilogue
 
 Parameter gradients are written straight into ``param.grad`` (fp32; accumulated when it already
@@ -42,13 +42,11 @@ PARAM_EPOCH = 0
 # launch per iteration.  SF_PACK_PLAN=0 keeps the per-layer launches (A/B).
 PACK_RECORD = None
 PACK_PLAN = os.environ.get("SF_PACK_PLAN", "1") != "0"
-# Intermediate activations of a block (relu(bn_a(ya)), relu(bn_b(yb))) are materialised in fp16 (default) or recomputed
-# in the consumer's operand loads (SF_MATERIALIZE=0, the round-1 schedule; kept for A/B runs).
-MATERIALIZE = os.environ.get("SF_MATERIALIZE", "1") != "0"
 # The reduction pass of an inner BatchNorm's backward (sums of g and g * y) is taken in the epilogue of the data gradient that
 # PRODUCES its input gradient (ops.conv_dgrad(..., bn=...)): one read of the y tile instead of a pass over dz and y, one launch
 # less per inner BatchNorm.  SF_BN_FUSE_REDUCE=0 keeps the separate sf_bn_bwd_reduce pass (A/B).
 BN_FUSE_REDUCE = os.environ.get("SF_BN_FUSE_REDUCE", "1") != "0"
+CAT_IN_PLACE = os.environ.get("SF_CAT_IN_PLACE", "1") != "0"       # ResBlockFn writes into FuseFn's buffer (A/B switch)
 # Backward segmentation (slowfast_amd.step.TrainStep): models call cut() on the activations that cross a stage boundary.
 # Normally the identity.  While a _Segments recorder is installed the tensors are replaced by detached leaves, so that the
 # backward pass can be run -- and captured into HIP graphs -- stage by stage (head + res5 first), and the gradient all-reduce
@@ -144,51 +142,7 @@ def cut(x):
     return SEGMENTS.cut([x])[0]
 
 
-# Weight gradients on a SIDE STREAM.  The backward critical path is the data-gradient chain (dgrad -> BatchNorm backward ->
-# dgrad ...); a layer's weight gradient depends on the same dy but nothing downstream depends on IT until the optimizer (or
-# the all-reduce of its bucket).  Forked to a second HIP stream it runs concurrently with the bandwidth-bound BatchNorm
-# backward / elementwise kernels of the chain -- an MFMA- and latency-bound kernel beside HBM-bound ones, the pairing that
-# actually overlaps.  Works under graph capture too (the fork / join become graph edges).  OPT-IN (SF_WGRAD_STREAM=1): on
-# ROCm 7.2 a replayed hipGraph runs the two branches back to back -- measured 734 vs 735 clips/s on SlowFast, 523 vs 524
-# on MViTv2-S, 1166 vs 1175 on X3D-M (profiles/r2/r2_v15_wgrad_stream_ab.txt) -- so the default keeps the single stream.
-# Re-measured at the end of round 6 (profiles/r6_v43_wgrad_stream_ab.txt): X3D-M 1493 vs 1502, MViTv2-S 757 vs 758, SlowFast 825 vs 870.
-WGRAD_STREAM = os.environ.get("SF_WGRAD_STREAM", "0") != "0"
-_side_streams = {}
-_side_keep = []          # tensors the side stream still reads: kept alive until the join (no allocator stream bookkeeping)
-_side_pending = set()    # devices with un-joined side-stream work
-_join_queued = False
-
-
-def _fork_wgrad(device):
-    """Side stream of `device`, ordered after everything already enqueued on the current stream."""
-    global _join_queued
-    side = _side_streams.get(device)
-    if side is None:
-        side = _side_streams[device] = torch.cuda.Stream(device=device)
-    side.wait_stream(torch.cuda.current_stream(device))
-    _side_pending.add(device)
-    if not _join_queued:
-        try:            # join when the backward pass that started this ends (plain ``loss.backward()`` callers)
-            torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
-            _join_queued = True
-        except RuntimeError:
-            pass        # not inside a backward pass: the caller joins explicitly
-    return side
-
-
-def join_side_streams():
-    """The current stream waits for the forked weight-gradient work; called at the end of every backward pass / backward
-    segment, and before parameters are announced final to a gradient reducer."""
-    global _join_queued
-    _join_queued = False
-    for device in list(_side_pending):
-        torch.cuda.current_stream(device).wait_stream(_side_streams[device])
-    _side_pending.clear()
-    _side_keep.clear()
-    for device in {d for d, _ in _pathway_streams}:
-        _join_pathways(device)
-
-
+# ---- HIP streams: every fork, every join and all their state ---------------------------------------------------------------
 # Independent PATHWAYS on their own HIP streams (round 5).  Between two lateral connections the Slow and the Fast pathway of a
 # SlowFast stage do not depend on each other (slowfast/models/video_model_builder.py:423-441: s_i runs every pathway, s_i_fuse
 # joins them), in forward and in backward.  Issued on ONE stream their kernels run back to back: the Slow pathway's MFMA-bound
@@ -197,75 +151,58 @@ def join_side_streams():
 # graph BRANCHES under a captured step -- and fill each other's holes: SlowFast-8x8-R50 41.4 -> 38.7 ms per step
 # (profiles/r5_v4_pathway_streams_probe.txt, r5_v5_pathway_streams_ab.txt; the per-pair probe of round 2 had predicted 7 %).  run_pathways() forks before and joins
 # after a stage; autograd runs every backward node on the stream of its forward, so the backward forks and joins by itself.
+# Independent BRANCHES inside a block (the q and the k / v pooling chains of MultiScaleAttention, attention.py:13-45, 320-351:
+# three depthwise convolutions + LayerNorms on disjoint channel slices of qkv) on two streams: each of these launches covers a few
+# hundred workgroups on a 256-CU chip -- side by side they fill it.  Same fork / join discipline (run_branches).
 # Rules that keep it exact: scratch memory is per stream (ops._workspace), parameter-gradient consumers join every stream first
 # (join_side_streams), tensors that cross a fork / join stay referenced by autograd until their consumers are enqueued.
-# SF_PATHWAY_STREAMS=0: one stream (A/B runs).
+# SF_PATHWAY_STREAMS=0 / SF_BRANCH_STREAMS=0: one stream (A/B runs).
 PATHWAY_STREAMS = os.environ.get("SF_PATHWAY_STREAMS", "1") != "0"
-CAT_IN_PLACE = os.environ.get("SF_CAT_IN_PLACE", "1") != "0"       # ResBlockFn writes into FuseFn's buffer (A/B switch)
-_pathway_streams = {}    # (device, pathway) -> stream
-_pathway_main = {}       # device -> the stream the last fork left from
+BRANCH_STREAMS = os.environ.get("SF_BRANCH_STREAMS", "1") != "0"
+_pathway_streams = {}    # (device, key) -> stream; key = the pathway number p, or ("branch", i)
+_pathway_main = {}       # device -> the stream the last PATHWAY fork left from
+_join_task = -1          # autograd graph task (one per backward pass) whose end-of-pass join is queued; -1: none outstanding
 
 
-def _pathway_stream(device, p):
-    s = _pathway_streams.get((device, p))
-    if s is None:
-        s = _pathway_streams[(device, p)] = torch.cuda.Stream(device=device)
-    return s
+def _fork_join(dev, keys, thunks):
+    """[t() for t in thunks] -- thunks[0] on the current stream, thunks[i] on the stream cached under (dev, keys[i]), forked after
+    everything already enqueued on the current stream and joined before this returns.  Under capture the waits are graph edges."""
+    main = torch.cuda.current_stream(dev)
+    outs = [None] * len(thunks)
+    sides = []
+    for i in range(1, len(thunks)):
+        side = _pathway_streams.get((dev, keys[i]))
+        if side is None:
+            side = _pathway_streams[(dev, keys[i])] = torch.cuda.Stream(device=dev)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            outs[i] = thunks[i]()
+        sides.append(side)
+    outs[0] = thunks[0]()
+    for side in sides:
+        main.wait_stream(side)
+    return outs
 
 
 def run_pathways(n, fn, like):
-    """[fn(p) for p in range(n)] -- pathway 0 on the current stream, pathways 1 .. n-1 each on its own side stream, forked after
-    everything already enqueued on the current stream and joined before this returns.  ``like``: a tensor that tells the device
-    (CPU tensors / one pathway / SF_PATHWAY_STREAMS=0: a plain loop)."""
+    """[fn(p) for p in range(n)] -- pathway 0 on the current stream, pathways 1 .. n-1 each on its own side stream.  ``like``: a
+    tensor that tells the device (CPU tensors / one pathway / SF_PATHWAY_STREAMS=0: a plain loop)."""
     if not (PATHWAY_STREAMS and n > 1 and like.is_cuda):
         return [fn(p) for p in range(n)]
-    dev = like.device
-    main = torch.cuda.current_stream(dev)
-    _pathway_main[dev] = main
-    outs = [None] * n
-    sides = []
-    for p in range(1, n):
-        side = _pathway_stream(dev, p)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            outs[p] = fn(p)
-        sides.append(side)
-    outs[0] = fn(0)
-    for side in sides:
-        main.wait_stream(side)
-    return outs
-
-
-# Independent BRANCHES inside a block (the q and the k / v pooling chains of MultiScaleAttention, attention.py:13-45, 320-351:
-# three depthwise convolutions + LayerNorms on disjoint channel slices of qkv) on two streams: each of these launches covers a few
-# hundred workgroups on a 256-CU chip -- side by side they fill it.  Same fork / join discipline as run_pathways.
-BRANCH_STREAMS = os.environ.get("SF_BRANCH_STREAMS", "1") != "0"
+    _pathway_main[like.device] = torch.cuda.current_stream(like.device)
+    return _fork_join(like.device, range(n), [functools.partial(fn, p) for p in range(n)])
 
 
 def run_branches(fns, like):
-    """[fn() for fn in fns] -- fns[0] on the current stream, the others each on a side stream, forked after everything already
-    enqueued and joined before this returns."""
+    """[fn() for fn in fns] -- fns[0] on the current stream, the others each on a side stream."""
     if not (BRANCH_STREAMS and len(fns) > 1 and like.is_cuda):
         return [fn() for fn in fns]
-    dev = like.device
-    main = torch.cuda.current_stream(dev)
-    outs = [None] * len(fns)
-    sides = []
-    for i in range(1, len(fns)):
-        side = _pathway_stream(dev, ("branch", i))
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            outs[i] = fns[i]()
-        sides.append(side)
-    outs[0] = fns[0]()
-    for side in sides:
-        main.wait_stream(side)
-    return outs
+    return _fork_join(like.device, [("branch", i) for i in range(len(fns))], fns)
 
 
 def _join_pathways(device):
-    """The CURRENT stream of ``device`` waits for every pathway stream and for the stream they were forked from: whatever it
-    enqueues next (a gradient all-reduce, an optimizer pass) sees the gradients of all pathways."""
+    """The CURRENT stream of ``device`` waits for every pathway / branch stream and for the stream the pathways were forked from:
+    whatever it enqueues next (a gradient all-reduce, an optimizer pass) sees the gradients of all of them."""
     cur = torch.cuda.current_stream(device)
     for (d, _), s in _pathway_streams.items():
         if d == device and s != cur:
@@ -273,6 +210,32 @@ def _join_pathways(device):
     main = _pathway_main.get(device)
     if main is not None and main != cur:
         cur.wait_stream(main)
+
+
+def join_side_streams():
+    """The current stream of every device waits for its pathway and branch streams; called at the end of every backward pass /
+    backward segment, and before parameters are announced final to a gradient reducer."""
+    global _join_task
+    _join_task = -1
+    for device in {d for d, _ in _pathway_streams}:
+        _join_pathways(device)
+
+
+def _queue_join_at_end_of_backward():
+    """Backward nodes of the Fast pathway / of the k-v branch write param.grad in place on THEIR streams.  TrainStep and the
+    reducer join explicitly; a plain ``loss.backward(); optimizer.step()`` caller does not, so the join rides on the backward
+    pass itself: whatever the caller enqueues after ``backward()`` returns sees every pathway's gradients.  (before
+    this it held only because autograd's leaf-stream synchronisation happened to cover the AccumulateGrad nodes created under
+    the side stream.)  Queued once per PASS, not per process: a pass that raises never runs its callbacks, and the next pass -- a
+    new graph task -- must queue its own (ADVICE r6 finding 2)."""
+    global _join_task
+    if not _pathway_streams:
+        return
+    task = torch._C._current_graph_task_id()
+    if task == -1 or task == _join_task:
+        return          # not inside a backward pass (the caller joins explicitly), or this pass has its join already
+    torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
+    _join_task = task
 
 
 # Test hook: when a list, every Function with a ReLU or a max-pool appends the tensors that decide its backward routing (raw conv
@@ -313,27 +276,11 @@ def _always():
     return True
 
 
-def _queue_join_at_end_of_backward():
-    """Backward nodes of the Fast pathway / of the k-v branch write param.grad in place on THEIR streams.  TrainStep and the
-    reducer join explicitly; a plain ``loss.backward(); optimizer.step()`` caller does not, so the join rides on the backward
-    pass itself (the same end-of-pass callback the side-stream weight gradients use): whatever the caller enqueues after
-    ``backward()`` returns sees every pathway's gradients.  (before this it held only because autograd's leaf-stream
-    synchronisation happened to cover the AccumulateGrad nodes created under the side stream.)"""
-    global _join_queued
-    if _join_queued or not _pathway_streams:
-        return
-    try:
-        torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
-        _join_queued = True
-    except RuntimeError:
-        pass            # not inside a backward pass (a segment driven by TrainStep, which joins itself)
-
-
 def _notify(params):
     _queue_join_at_end_of_backward()
     if GRADS_VIA_AUTOGRAD:          # the consumer of the gradients (DDP's reducer) hooks autograd itself
         return
-    if (_side_pending or _pathway_streams) and any(getattr(fn, "needs_join", _always)() for fn in _listeners):
+    if _pathway_streams and any(getattr(fn, "needs_join", _always)() for fn in _listeners):
         join_side_streams()         # a listener is about to start the all-reduce of these gradients: they must be complete
     if _sub_passes > 1:
         final = []
@@ -540,13 +487,7 @@ class ConvUnit:
         w = self.conv.weight
         if w.requires_grad:
             dw, zero_first = _grad_dest(w)
-            if WGRAD_STREAM and x.is_cuda and not GRADS_VIA_AUTOGRAD:
-                side = _fork_wgrad(x.device)
-                _side_keep.extend((x, dy))
-                with torch.cuda.stream(side):
-                    ops.conv_wgrad(x, dy, geom, dw, in_affine=in_affine, out_scale=1.0, zero_first=zero_first, side=True)
-            else:
-                ops.conv_wgrad(x, dy, geom, dw, in_affine=in_affine, out_scale=1.0, zero_first=zero_first)
+            ops.conv_wgrad(x, dy, geom, dw, in_affine=in_affine, out_scale=1.0, zero_first=zero_first)
         if not need_dx:
             return None
         _, wd = self.weights(geom)
@@ -783,7 +724,7 @@ class FuseFn(torch.autograd.Function):
 class ResBlockFn(torch.autograd.Function):
     """relu(shortcut(x) + transform(x)) (slowfast/models/resnet_helper.py:512-521) for a transform that is a chain of
     conv -> BN [-> ReLU] units ending in the block-final BN: BottleneckTransform (a, b, c; :377-392) and BasicTransform
-    (a, b; :105-115).  Every unit after the first applies its producer's BatchNorm + ReLU in its operand loads."""
+    (a, b; :105-115).  Every unit after the first reads its producer's relu(bn(y)), written once in fp16."""
 
     @staticmethod
     def forward(ctx, x, mod, *params):
@@ -794,21 +735,16 @@ class ResBlockFn(torch.autograd.Function):
         x = as_cl(x)
         units, P = mod.branch2._chain, mod._proj
         tr = mod.training
-        raw, bn, act = [], [], []
-        h, prologue = x, None
+        raw, bn, act, h = [], [], [], x
         for i, u in enumerate(units):
-            h, st = u.forward(h, prologue, tr)
+            h, st = u.forward(h, None, tr)
             raw.append(h)
             bn.append(st)
-            if MATERIALIZE and i + 1 < len(units):
+            if i + 1 < len(units):
                 # z = relu(bn(y)) written once (C/4-wide tensors): the consumer convolution and its weight gradient
                 # then read a plain operand -- direct-to-LDS copies, no per-element work in the GEMM loaders
                 h = ops.bn_act(h, st.scale, st.shift, relu=True)
                 act.append(h)
-                prologue = None
-            else:
-                act.append(None)
-                prologue = (st.scale, st.shift, True)
         yc, sc = raw[-1], bn[-1]
         # the backward pass needs only the SIGN of the block output (ReLU mask): one bit per element, written here, stands
         # in for two full reads of `out` in BatchNorm backward (and for the masked gradient tensor of the identity shortcut)
@@ -860,12 +796,10 @@ class ResBlockFn(torch.autograd.Function):
             dy1 = P.bn_backward(dout, y1, s1, zmask=bits)
         for i in range(last, 0, -1):
             part = None
-            if act[i - 1] is not None and BN_FUSE_REDUCE and _sync_of(units[i - 1].bn) is None:
+            if BN_FUSE_REDUCE and _sync_of(units[i - 1].bn) is None:
                 d_in, part = units[i].backward(act[i - 1], None, dy, need_dx=True, bn_fuse=(raw[i - 1], bn[i - 1]))
-            elif act[i - 1] is not None:
-                d_in = units[i].backward(act[i - 1], None, dy, need_dx=True)
             else:
-                d_in = units[i].backward(raw[i - 1], (bn[i - 1].scale, bn[i - 1].shift, True), dy, need_dx=True)
+                d_in = units[i].backward(act[i - 1], None, dy, need_dx=True)
             dy = units[i - 1].bn_backward(d_in, raw[i - 1], bn[i - 1], relu_self=True, part=part)
         prev = ctx.prev_bn if need_dx else None
         if prev is not None and prev["sync"]:      # the PRODUCER's BatchNorm reduces its sums across ranks: not fused

@@ -7,12 +7,8 @@ import torch
 import torch.nn as nn
 
 from . import engine, ops
-import os
 
 from .lib import get_lib
-
-# the training-crop average pool of ResNetBasicHead on sf_tmean_* (SF_HEAD_FUSED_MEAN=0: torch fp32 ops, the round 1-5 path)
-FUSED_MEAN = os.environ.get("SF_HEAD_FUSED_MEAN", "1") != "0"
 
 
 class _GlobalMeanFn(torch.autograd.Function):
@@ -77,7 +73,7 @@ class ResNetBasicHead(nn.Module):
         for i, x in enumerate(inputs):
             pool = getattr(self, f"pathway{i}_avgpool")
             full = isinstance(pool, nn.AdaptiveAvgPool3d) or tuple(pool.kernel_size) == tuple(x.shape[2:])
-            if full and _GlobalMeanFn.eligible(x) and FUSED_MEAN:
+            if full and _GlobalMeanFn.eligible(x):         # the training-crop average pool on sf_tmean_*
                 pooled.append(_GlobalMeanFn.apply(x))
             elif full and x.dim() == 5 and x.stride(1) == 1:
                 # the pool window is the whole (T,H,W) extent (training crop): mean over the channels-last rows

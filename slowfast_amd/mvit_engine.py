@@ -26,19 +26,10 @@ _f16 = _sflib.act_dtype()        # fp16, or bf16 under SF_ACT_DTYPE=bf16 (lib.AC
 # pool_k and pool_v of a block in ONE launch per direction (tokens.dwconv_*_pair).  Measured in the step
 # (profiles/r6_v27_pair_kv_ab.txt): +1.2 % on MViT-B-16x4, whose blocks mostly pool k / v only -- the two chains then run back to
 # back on one stream -- and -0.5 % on MViTv2-S, where every block also pools q: the k / v chains already hide behind the longer q
-# chain on a second stream (engine.run_branches) and one 768-workgroup launch disturbs it more than two of 384.  So: "auto" =
-# paired only in blocks without a q pooling branch; SF_PAIR_KV=1 always, 0 never (A/B runs).
-PAIR_KV = os.environ.get("SF_PAIR_KV", "auto")
-# SF_BIAS_FROM_POOL=0: the qkv bias gradient from a pass over d(qkv) (sf_colsum) instead of from the column sums the pooling data
-# gradients leave (A/B runs; profiles/r6_v31_bias_from_pool_ab.txt)
-BIAS_FROM_POOL = os.environ.get("SF_BIAS_FROM_POOL", "1") != "0"
-
-
+# chain on a second stream (engine.run_branches) and one 768-workgroup launch disturbs it more than two of 384.  So: paired only
+# in blocks without a q pooling branch.
 def _pair_kv(plan):
-    return PAIR_KV == "1" or (PAIR_KV not in ("0", "1") and plan.gq is None)
-# fc1's bias gradient from the epilogue of the GEMM that produces d(loss)/d(fc1 output) (tokens.gemm_gelu_grad(dbias=...))
-# instead of a separate column-sum pass over it; SF_FUSE_COLSUM=0 keeps the pass (A/B)
-FUSE_COLSUM = os.environ.get("SF_FUSE_COLSUM", "1") != "0"
+    return plan.gq is None
 
 
 # fp32 side copy of the residual stream: the reference adds the two branch outputs of a MultiScaleBlock to an fp32 stream
@@ -151,7 +142,7 @@ class LinearUnit:
             db, zero_first = _grad_dest(lin.bias)
             tokens.bias_grad(dy, db, accumulate=not zero_first)
         _, wt = self._ops()
-        if consumer_bias is not None and consumer_bias.requires_grad and FUSE_COLSUM:
+        if consumer_bias is not None and consumer_bias.requires_grad:
             # the result IS d(loss)/d(output of the Linear in front of the GELU): its bias gradient = the column sums of the tile
             # the epilogue stores (one launch instead of a pass over the widest gradient tensor of the block)
             dcb, zf = _grad_dest(consumer_bias)
@@ -324,10 +315,6 @@ class AttentionPlan:
 # the dK/dV kernel) lost to the unfused chain, 414 vs 445 clips/s (profiles/r1/r1_visit12_bench_mvit_*.json); with the
 # bias on the matrix cores, exp2, lazy rescale and the query split it wins, 488 vs 439 (profiles/r1/r1_visit13_*).
 _FUSED_DEFAULT = "1"
-# GELU in the fc1 GEMM epilogue / gelu' in the fc2 data-gradient epilogue (SF_GELU_FUSED=0: separate elementwise passes)
-_FUSED_GELU = os.environ.get("SF_GELU_FUSED", "1") != "0"
-# bias gradients of mlp.fc2 / attn.proj from the column sums norm2's backward takes in passing (SF_LN_BIAS_SUMS=0: separate passes)
-_LN_BIAS_SUMS = os.environ.get("SF_LN_BIAS_SUMS", "1") != "0"
 
 
 def _fused_attention(plan):
@@ -504,9 +491,7 @@ def attention_backward(att, plan, qkv, sv, do):
 
     def pool_back(i, dy, pool, geom):                        # depthwise pooling backward into slice i of d(qkv)
         x_in = qkv[..., i * C:(i + 1) * C]
-        res = tokens.dwconv_dgrad(dy.view(-1, C), pool.weight, geom, out=dqkv[..., i * C:(i + 1) * C], sums=BIAS_FROM_POOL)
-        if BIAS_FROM_POOL:
-            bias_parts[i] = res[1]
+        bias_parts[i] = tokens.dwconv_dgrad(dy.view(-1, C), pool.weight, geom, out=dqkv[..., i * C:(i + 1) * C], sums=True)[1]
         dw, zero_first = _grad_dest(pool.weight)
         tokens.dwconv_wgrad(x_in, dy.view(-1, C), geom, dw, zero_first=zero_first)
 
@@ -644,11 +629,7 @@ class MultiScaleBlockFn(torch.autograd.Function):
         else:                                              # x_res + drop_path(attention output), attention.py:500-502
             x1 = tokens.row_scale_add(att._proj.forward(o), drop[0], xres.shape[1], resid=xres, side=s1)
         xn2, m2, r2 = mod._norm2.forward(x1, side=side1.reader(Nq) if side1 is not None else None)
-        if _FUSED_GELU:
-            h, a = mod.mlp._fc1.forward_gelu(xn2)
-        else:
-            h = mod.mlp._fc1.forward(xn2)
-            a = tokens.gelu_fwd(h)
+        h, a = mod.mlp._fc1.forward_gelu(xn2)              # GELU in the fc1 GEMM epilogue
         # MViTv1 (DIM_MUL_IN_ATT False): the dimension change acts on the normed Mlp input (attention.py:507-508)
         xb = mod._proj.forward(xn2) if proj_last else x1
         s2 = side2 = None
@@ -688,13 +669,9 @@ class MultiScaleBlockFn(torch.autograd.Function):
         proj_last = mod._proj is not None and not proj_first
         # Without stochastic depth, norm2's backward reads d(block output) as its residual operand and writes d(x1): their column
         # sums ARE the bias gradients of mlp.fc2 and attn.proj -- taken from that pass instead of two column-sum passes (round 4)
-        ln_sums = drop is None and not proj_last and _LN_BIAS_SUMS
-        if _FUSED_GELU:
-            dh, b1_done = mod.mlp._fc2.backward_through_gelu(sv["a"], dbr, sv["h"], consumer_bias=mod.mlp.fc1.bias,
-                                                            bias_done=ln_sums)
-        else:
-            da = mod.mlp._fc2.backward(sv["a"], dbr, bias_done=ln_sums)
-            dh, b1_done = tokens.gelu_bwd(sv["h"], da), False
+        ln_sums = drop is None and not proj_last
+        # gelu' in the fc2 data-gradient epilogue
+        dh, b1_done = mod.mlp._fc2.backward_through_gelu(sv["a"], dbr, sv["h"], consumer_bias=mod.mlp.fc1.bias, bias_done=ln_sums)
         dxn2 = mod.mlp._fc1.backward(sv["xn2"], dh, bias_done=b1_done)
         if proj_last:                                      # the skip path went through proj(norm2(x1))
             dxn2 = mod._proj.backward(sv["xn2"], dout, resid=dxn2)
@@ -755,19 +732,12 @@ def _attention_sub_backward(sub, plan, sv, d_out, resid=None):
 def _mlp_sub_forward(sub, x):
     """MLPSubblock.forward (reversible_mvit.py:616-617) up to (not including) fc2 -> (gelu(fc1(norm(x))), saved)."""
     xn, m, r = sub._norm.forward(x)
-    if _FUSED_GELU:
-        h, a = sub.mlp._fc1.forward_gelu(xn)
-    else:
-        h = sub.mlp._fc1.forward(xn)
-        a = tokens.gelu_fwd(h)
+    h, a = sub.mlp._fc1.forward_gelu(xn)
     return a, dict(x=x, xn=xn, st=(m, r), h=h, a=a)
 
 
 def _mlp_sub_backward(sub, sv, d_out, resid=None):
-    if _FUSED_GELU:
-        dh, b1_done = sub.mlp._fc2.backward_through_gelu(sv["a"], d_out, sv["h"], consumer_bias=sub.mlp.fc1.bias)
-    else:
-        dh, b1_done = tokens.gelu_bwd(sv["h"], sub.mlp._fc2.backward(sv["a"], d_out)), False
+    dh, b1_done = sub.mlp._fc2.backward_through_gelu(sv["a"], d_out, sv["h"], consumer_bias=sub.mlp.fc1.bias)
     dxn = sub.mlp._fc1.backward(sv["xn"], dh, bias_done=b1_done)
     return sub._norm.backward(dxn, sv["x"], *sv["st"], resid=resid)
 

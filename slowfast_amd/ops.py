@@ -276,8 +276,8 @@ _workspaces = {}
 _retired_workspaces = []
 
 
-def _workspace(device, nbytes, key=None):
-    """One grow-only scratch buffer per device: every user is enqueued on the same stream, so launches that
+def _workspace(device, nbytes):
+    """One grow-only scratch buffer per (device, stream): every user is enqueued on the same stream, so launches that
     share it are ordered (the callee allocates nothing, SURVEY.md 8b 'Ownership').
 
     A captured HIP graph (slowfast_amd.step.TrainStep) bakes the buffer's ADDRESS into its kernel nodes.  When a later,
@@ -285,10 +285,10 @@ def _workspace(device, nbytes, key=None):
     allocator): a graph captured earlier keeps writing its split-K partials into memory that is still reserved for
     exactly that, instead of into whatever tensor the allocator would have placed there.  Growth happens a handful of
     times per process (the largest layer geometry wins), so the retained memory is bounded by ~2x the final size."""
-    # launches on different streams (engine.run_pathways, engine.WGRAD_STREAM) must not share scratch memory: one buffer per
+    # launches on different streams (engine.run_pathways, engine.run_branches) must not share scratch memory: one buffer per
     # (device, stream) -- a captured graph bakes the stream's buffer into its branch
     sid = torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0
-    k = (device, key, sid)
+    k = (device, sid)
     ws = _workspaces.get(k)
     if ws is None or ws.numel() < nbytes:
         if ws is not None:
@@ -298,7 +298,7 @@ def _workspace(device, nbytes, key=None):
     return ws
 
 
-def conv_wgrad(x, dy, geom, dw, in_affine=None, out_scale=1.0, zero_first=True, side=False):
+def conv_wgrad(x, dy, geom, dw, in_affine=None, out_scale=1.0, zero_first=True):
     """dw (+)= out_scale * d(loss)/d(weight); dw is an fp32 tensor shaped like the Conv3d weight."""
     assert tuple(x.shape) == geom.in_shape and tuple(dy.shape) == geom.out_shape
     assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == geom.Cow * geom.Cw * geom.taps
@@ -307,7 +307,7 @@ def conv_wgrad(x, dy, geom, dw, in_affine=None, out_scale=1.0, zero_first=True, 
     d = geom.desc(cl_ld(x), cl_ld(dy))
     if geom.ws_bytes is None:
         geom.ws_bytes = lib.call("sf_conv_wgrad_workspace", byref(d))
-    ws = _workspace(x.device, geom.ws_bytes, "wgrad-side" if side else None)
+    ws = _workspace(x.device, geom.ws_bytes)
     lib.call("sf_conv_wgrad", byref(d), x.data_ptr(), _ptr(sc), _ptr(sh), relu,
                    dy.data_ptr(), dw.data_ptr(), float(out_scale), int(zero_first), ws.data_ptr(), ws.numel(),
                    _ptr(_wgrad_rowtab(geom, d, x.device)) if sc is None else None, _stream(x),

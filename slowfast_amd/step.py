@@ -114,7 +114,7 @@ class TrainStep:
         # FlatOptimizer: the (dynamic) loss scale is a device scalar -- a captured graph reads its current value at replay
         scale = self.optimizer.loss_scale if self._flat else self.loss_scale
         (loss * scale).backward()
-        engine.join_side_streams()      # weight gradients forked to the side stream (engine.WGRAD_STREAM)
+        engine.join_side_streams()      # the pathway / branch streams that wrote gradients (engine.run_pathways, run_branches)
         return logits, loss
 
     # ---- segmented iteration --------------------------------------------------------------------------------------

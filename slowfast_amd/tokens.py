@@ -182,12 +182,10 @@ def layernorm_fwd(x, gamma, beta, eps, out=None, save_stats=True, side=None):
     return y, mean, rstd
 
 
-# Deferred finalizes (SF_FIN_BATCH=0: every finalize is its own launch, A/B runs).  Inside ``with deferred_finalizes():`` the
+# Deferred finalizes.  Inside ``with deferred_finalizes():`` the
 # column-sum finalizes of bias / LayerNorm-affine gradients are collected and issued as ONE sf_colsum_finalize_batch launch when
 # the context exits (mvit_engine wraps the backward of a block in it: ~9 launches of 6-7 us become one).  The partial tables
 # and outputs are kept alive by the pending list; two finalizes into the same output are never batched together.
-import os as _os
-_FIN_BATCH = _os.environ.get("SF_FIN_BATCH", "1") != "0"
 _pending_fin = None         # list of (ColFinItem fields..., tensors kept alive) while a deferral context is open
 _FIN_MAX_ROWS = 2048        # tables up to this many rows are batched (longer ones keep their own launch with its fold stage)
 
@@ -202,7 +200,7 @@ class deferred_finalizes:
     def __enter__(self):
         global _pending_fin
         self._outer = _pending_fin
-        if _FIN_BATCH and _pending_fin is None:
+        if _pending_fin is None:
             _pending_fin = []
         return self
 

@@ -25,8 +25,6 @@ from .video_models import get_norm, init_weights
 
 _f16 = _sflib.act_dtype()        # fp16, or bf16 under SF_ACT_DTYPE=bf16 (lib.ACT_MODE)
 
-# SF_GATE_BN_FUSE=0: the separate sf_bn_bwd_reduce pass behind sf_gate_act_bwd (A/B runs; profiles/r6_v22_gate_bn_fuse_ab.txt)
-GATE_BN_FUSE = os.environ.get("SF_GATE_BN_FUSE", "1") != "0"
 # SF_SE_FROM_STATS=0: the SE squeeze as a pass of its own over the activation (sf_sample_mean) instead of from the depthwise
 # convolution's statistics table (A/B runs; profiles/r6_v24_se_from_stats_ab.txt)
 SE_FROM_STATS = os.environ.get("SF_SE_FROM_STATS", "1") != "0"
@@ -200,7 +198,7 @@ def gate_bn_backward(t, yb, sb, gate, se, ysum, dzb):
         if t._se is not None:
             dgate = gate_grad(yb, sb.scale, sb.shift, dzb, gate, t._swish_inner)
             dmean = t._se.gate_bwd(se[0], se[1], gate, dgate)
-        if engine.BN_FUSE_REDUCE and GATE_BN_FUSE:  # the reduction of b_bn's backward rides on the gate / Swish backward pass
+        if engine.BN_FUSE_REDUCE:                   # the reduction of b_bn's backward rides on the gate / Swish backward pass
             du, part_b = gate_act_bwd(yb, sb.scale, sb.shift, gate, t._swish_inner, dzb, dmean, bn_part=True)
         else:
             du, part_b = gate_act_bwd(yb, sb.scale, sb.shift, gate, t._swish_inner, dzb, dmean), None

@@ -280,3 +280,38 @@ def test_lateral_concat_written_in_place(sim, monkeypatch):
     assert res[False][2] - res[True][2] == 3, "one copy per lateral connection after res2 / res3 / res4"
     assert torch.equal(res[True][0], res[False][0])
     assert all(torch.equal(a, b) for a, b in zip(res[True][1], res[False][1]))
+
+
+def test_end_of_backward_join_survives_a_failed_backward(monkeypatch):
+    """engine._notify queues join_side_streams once per backward PASS.  A pass that raises never runs its end-of-pass callbacks;
+    the passes after it must still queue -- and run -- their own join, and none may be left marked as queued (a process-wide
+    "queued" flag stuck at True after the failure, and every later plain ``loss.backward(); optimizer.step()`` skipped the join
+    of the Fast-pathway / k-v-branch streams)."""
+    import torch
+    from slowfast_amd import engine
+    joined = []
+    monkeypatch.setitem(engine._pathway_streams, ("dummy-device", 1), None)     # "a side stream exists"
+    monkeypatch.setattr(engine, "_join_pathways", joined.append)                # join_side_streams and _notify stay real
+
+    class Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, fail):
+            ctx.fail = fail
+            return x.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            engine._notify([])
+            if ctx.fail:
+                raise ValueError("backward failed")
+            return g, None
+
+    x = torch.ones(2, requires_grad=True)
+    Fn.apply(x, False).sum().backward()
+    assert joined == ["dummy-device"]
+    with pytest.raises(ValueError, match="backward failed"):
+        Fn.apply(x, True).sum().backward()
+    assert joined == ["dummy-device"]
+    Fn.apply(x, False).sum().backward()
+    assert joined == ["dummy-device"] * 2
+    assert engine._join_task == -1, "a join is still marked as queued"

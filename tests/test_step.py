@@ -356,7 +356,7 @@ def test_plain_backward_joins_side_streams(gpu, monkeypatch, name, flag):
         assert l1 == l0, (rep, l0, l1)
         for a, b in zip(p0, p1):
             assert torch.equal(a, b), rep
-    assert engine._pathway_streams and not engine._join_queued
+    assert engine._pathway_streams and engine._join_task == -1          # no join is left outstanding after the loop
 
 
 def test_static_clone_keeps_wpair_tag_and_strides():
