@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 31
+#define SF_ABI_VERSION 32
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -122,6 +122,25 @@ int sf_conv_wgrad_rowtab(const sf_conv_desc* d, void* tab, sf_stream_t stream);
 int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* in_scale, const float* in_shift, int in_relu,
                   const void* dy, float* dw, float out_scale, int zero_first, void* workspace, int64_t workspace_bytes,
                   const void* rowtab, sf_stream_t stream);
+/* Block-final BatchNorm backward fused into both gradients of the block's last convolution (ABI 32; resnet_helper.py:361-369,
+ * :512-521).  Replaces the three calls sf_bn_bwd_apply(dz, mask_bits, yc, coef) -> dy_c, sf_conv_wgrad(act, dy_c) and
+ * sf_conv_dgrad_bn(dy_c, wd) for a 1x1x1 unit-stride unpadded convolution d: dy_c = (f16)(k1 * g + k2 + k3 * yc) is formed per row
+ * tile on chip, rounded exactly as sf_bn_bwd_apply stores it, and never written to memory.
+ * sf_conv_c_bwd_plan: 1 when d takes this path (Ci % 8 == 0 <= 64, Co % 32 == 0 <= 256, no fused input BatchNorm (in_affine == 0),
+ * the 1-bit form of the block-output mask (mask_bits != 0); never a function of the row count), else 0 (the caller keeps the three
+ * calls); *tile_rows = rows per row tile, *workspace_bytes = size of `workspace`.
+ * sf_conv_c_bwd: dz [M][lddz] gradient w.r.t. the block output, mask_bits [M][Co/8] (sf_bn_act), yc [M][ldyc] the raw output of d,
+ * coef [3][Co] from sf_bn_bwd_finalize, act [M][d->ldx] the input of d, wd the packed data-gradient operand.  Outputs: d_in
+ * [M][ld_in] (d->ldy is not used), dw as sf_conv_wgrad writes it (out_scale, zero_first).  Optional (bn_part != NULL), exactly as
+ * sf_conv_dgrad_bn with mask_scale / mask_shift: the sums of g and g * bn_y over the stored d_in, g = d_in under
+ * (bn_y * bn_scale + bn_shift > 0), one row [2][Ci] per row tile in tile order; bn_part_rows >= ceil(M / tile_rows);
+ * *bn_rows (HOST pointer) = rows written.  Deterministic: no atomics, fixed summation order for a given workgroup count. */
+int sf_conv_c_bwd_plan(const sf_conv_desc* d, int in_affine, int mask_bits, int32_t* tile_rows, int64_t* workspace_bytes);
+int sf_conv_c_bwd(const sf_conv_desc* d, const void* dz, int32_t lddz, const void* mask_bits, const void* yc, int32_t ldyc,
+                  const float* coef, const void* act, const void* wd, const float* bn_scale, const float* bn_shift,
+                  const void* bn_y, int32_t bn_ldy, float* bn_part, int32_t bn_part_rows, int32_t* bn_rows, void* d_in,
+                  int32_t ld_in, float* dw, float out_scale, int zero_first, void* workspace, int64_t workspace_bytes,
+                  sf_stream_t stream);
 
 /* ---- BatchNorm3d -- replaces nn.BatchNorm3d built by batchnorm_helper.py:16-37 (get_norm) at every
  * *_bn call site of resnet_helper.py / stem_helper.py / video_model_builder.py:155-159, plus the

@@ -5,6 +5,7 @@
 #include "sf_igemm.h"
 #include "sf_igemm2.h"
 #include "sf_wgrad2.h"
+#include "sf_cbwd.h"
 #include "sf_pool.h"
 #include "sf_dwconv.h"
 #include "sf_dwsweep.h"
@@ -947,6 +948,130 @@ extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* 
     const int per_block = SF_THREADS / lanes;
     hipLaunchKernelGGL(sf_wgrad_reduce_kernel, dim3(cdiv(total, per_block)), dim3(SF_THREADS), 0, s, r);
     return check_launch("wgrad_reduce");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Block-final BatchNorm backward + both gradients of conv c in one persistent launch (sf_cbwd.h).  ONE planner decides who takes it:
+// 1x1x1, unit stride, unpadded, Ci % 8 == 0 <= 64, Co % 32 == 0 <= 256, a plain (already activated) input and the bit-mask form of
+// the block-output ReLU -- never the row count, so that small test models take the production path.  SF_CBWD=0 (test hook) keeps the
+// three launches; SF_CBWD_WGS (test hook) sets the workgroup count so that a small tensor makes every workgroup walk several tiles.
+// The rows are dealt to the workgroups exactly as sf_conv_wgrad deals them to its splits (plan_wgrad: contiguous runs of 32-row
+// chunks; plan_wgrad2's thin kernel: 128-row stages round robin, the four waves a quarter each), every 32-row MFMA step lands on the
+// accumulator it lands on there and the slabs meet in the same sf_wgrad_reduce_kernel launch: dw has the bits of the three-launch
+// path.  The inner BatchNorm's table keeps the 128-row tiles and the per-thread order of the data gradient's epilogue.
+struct CbwdPlan {
+    bool ok;
+    int cip, cop, R;
+    size_t ws_bytes;
+};
+#define SF_CBWD_MAX_WGS 1024
+template <int CIP, int COP>
+static void cbwd_fill(CbwdPlan& w) {
+    using K = CbwdCfg<CIP, COP>;
+    w.R = K::R;
+    w.ws_bytes = (size_t)SF_CBWD_MAX_WGS * COP * CIP * 4;
+}
+#define SF_CBWD_FOR_SHAPE(cip, cop, ...)                                                         \
+    do {                                                                                         \
+        if ((cip) == 16 && (cop) == 32) { constexpr int CIP_ = 16, COP_ = 32; __VA_ARGS__; }            \
+        else if ((cip) == 16 && (cop) == 64) { constexpr int CIP_ = 16, COP_ = 64; __VA_ARGS__; }       \
+        else if ((cip) == 16 && (cop) == 128) { constexpr int CIP_ = 16, COP_ = 128; __VA_ARGS__; }     \
+        else if ((cip) == 16 && (cop) == 256) { constexpr int CIP_ = 16, COP_ = 256; __VA_ARGS__; }     \
+        else if ((cip) == 32 && (cop) == 32) { constexpr int CIP_ = 32, COP_ = 32; __VA_ARGS__; }       \
+        else if ((cip) == 32 && (cop) == 64) { constexpr int CIP_ = 32, COP_ = 64; __VA_ARGS__; }       \
+        else if ((cip) == 32 && (cop) == 128) { constexpr int CIP_ = 32, COP_ = 128; __VA_ARGS__; }     \
+        else if ((cip) == 32 && (cop) == 256) { constexpr int CIP_ = 32, COP_ = 256; __VA_ARGS__; }     \
+        else if ((cip) == 64 && (cop) == 32) { constexpr int CIP_ = 64, COP_ = 32; __VA_ARGS__; }       \
+        else if ((cip) == 64 && (cop) == 64) { constexpr int CIP_ = 64, COP_ = 64; __VA_ARGS__; }       \
+        else if ((cip) == 64 && (cop) == 128) { constexpr int CIP_ = 64, COP_ = 128; __VA_ARGS__; }     \
+        else { constexpr int CIP_ = 64, COP_ = 256; __VA_ARGS__; }                                      \
+    } while (0)
+static CbwdPlan plan_cbwd(const sf_conv_desc* d, bool in_affine, bool mask_bits) {
+    CbwdPlan w;
+    memset(&w, 0, sizeof(w));
+    if (test_hook("SF_CBWD", 1) == 0) return w;
+    if (d->kT != 1 || d->kH != 1 || d->kW != 1 || d->sT != 1 || d->sH != 1 || d->sW != 1 || d->pT || d->pH || d->pW) return w;
+    if (d->To != d->Ti || d->Ho != d->Hi || d->Wo != d->Wi) return w;
+    if (d->Ci % 8 || d->Ci > 64 || d->Co % 32 || d->Co > 256) return w;
+    if (in_affine || !mask_bits) return w;
+    w.cip = d->Ci <= 16 ? 16 : d->Ci <= 32 ? 32 : 64;
+    w.cop = d->Co <= 32 ? 32 : d->Co <= 64 ? 64 : d->Co <= 128 ? 128 : 256;
+    SF_CBWD_FOR_SHAPE(w.cip, w.cop, (cbwd_fill<CIP_, COP_>(w)));
+    w.ok = true;
+    return w;
+}
+
+extern "C" int sf_conv_c_bwd_plan(const sf_conv_desc* d, int in_affine, int mask_bits, int32_t* tile_rows,
+                                  int64_t* workspace_bytes) {
+    if (check_desc(d)) return -1;
+    const CbwdPlan w = plan_cbwd(d, in_affine != 0, mask_bits != 0);
+    if (tile_rows) *tile_rows = w.ok ? 128 : 0;
+    if (workspace_bytes) *workspace_bytes = w.ok ? (int64_t)w.ws_bytes : 0;
+    return w.ok ? 1 : 0;
+}
+
+extern "C" int sf_conv_c_bwd(const sf_conv_desc* d, const void* dz, int32_t lddz, const void* mask_bits, const void* yc,
+                             int32_t ldyc, const float* coef, const void* act, const void* wd, const float* bn_scale,
+                             const float* bn_shift, const void* bn_y, int32_t bn_ldy, float* bn_part, int32_t bn_part_rows,
+                             int32_t* bn_rows, void* d_in, int32_t ld_in, float* dw, float out_scale, int zero_first,
+                             void* workspace, int64_t workspace_bytes, sf_stream_t stream) {
+    if (check_desc(d)) return -1;
+    REQUIRE(dz && mask_bits && yc && coef && act && wd && d_in && dw && workspace, "sf_conv_c_bwd: null pointer");
+    const CbwdPlan w = plan_cbwd(d, false, true);
+    REQUIRE(w.ok, "sf_conv_c_bwd: this geometry keeps sf_bn_bwd_apply + sf_conv_wgrad + sf_conv_dgrad_bn (sf_conv_c_bwd_plan == 0)");
+    REQUIRE(lddz >= d->Co && lddz % 8 == 0 && ldyc >= d->Co && ldyc % 8 == 0 && ld_in >= d->Ci && ld_in % 8 == 0,
+            "sf_conv_c_bwd: bad row pitch");
+    REQUIRE((((uintptr_t)dz | (uintptr_t)yc | (uintptr_t)act | (uintptr_t)wd | (uintptr_t)d_in | (uintptr_t)workspace) & 15) == 0,
+            "sf_conv_c_bwd: operands must be 16-byte aligned");
+    REQUIRE(workspace_bytes >= (int64_t)w.ws_bytes, "sf_conv_c_bwd: workspace too small (%lld < %lld bytes)",
+            (long long)workspace_bytes, (long long)w.ws_bytes);
+    const int64_t M = (int64_t)d->N * d->Ti * d->Hi * d->Wi;
+    const int ntiles = cdiv(M, 128);
+    const bool fuse = bn_part != nullptr;
+    if (fuse) {
+        REQUIRE(bn_scale && bn_shift && bn_y && bn_rows, "sf_conv_c_bwd: the fused reduction needs bn_scale, bn_shift, bn_y and bn_rows");
+        REQUIRE(bn_ldy >= d->Ci && bn_ldy % 8 == 0 && ((uintptr_t)bn_y & 15) == 0, "sf_conv_c_bwd: bad bn_y pitch / alignment");
+        REQUIRE(bn_part_rows >= ntiles, "sf_conv_c_bwd: the partial table needs ceil(positions / tile_rows) rows of [2][Ci] floats");
+    }
+    int32_t ldf, ldd;
+    sf_conv_weight_ld(d, &ldf, &ldd);
+    CbwdParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = (int)M; p.Ci = d->Ci; p.Co = d->Co;
+    p.dz = (const f16*)dz; p.lddz = lddz; p.bits = (const uint8_t*)mask_bits; p.yc = (const f16*)yc; p.ldyc = ldyc;
+    p.coef = coef; p.act = (const f16*)act; p.ldact = d->ldx; p.wd = (const f16*)wd; p.ldw = ldd;
+    if (fuse) { p.bnb_y = (const f16*)bn_y; p.bnb_ld = bn_ldy; p.bnb_scale = bn_scale; p.bnb_shift = bn_shift; p.bnb_part = bn_part; }
+    p.dx = (f16*)d_in; p.lddx = ld_in; p.ws = (float*)workspace; p.tiles128 = ntiles;
+    // who sums which rows: as the weight gradient of the three-launch path would (see above)
+    int wgs;
+    const Wgrad2Plan w2 = plan_wgrad2(d);
+    const int forced = test_hook("SF_CBWD_WGS", 0);
+    if (forced > 0) {
+        wgs = forced < SF_CBWD_MAX_WGS ? forced : SF_CBWD_MAX_WGS;
+        p.rps = roundup(cdiv(M, wgs), 32);
+        wgs = cdiv(M, p.rps);
+    } else if (w2.ok && w2.thin && w2.splits <= SF_CBWD_MAX_WGS) {
+        wgs = w2.splits; p.rps = 0;
+    } else {
+        const WgradPlan w1 = plan_wgrad(d);
+        wgs = w1.splits; p.rps = w1.chunks_per_split * 32;
+        REQUIRE(wgs <= SF_CBWD_MAX_WGS, "sf_conv_c_bwd: %d splits", wgs);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SF_CBWD_FOR_SHAPE(w.cip, w.cop, hipLaunchKernelGGL((sf_cbwd_kernel<CIP_, COP_>), dim3(wgs), dim3(SF_THREADS), 0, s, p));
+    if (check_launch("conv_c_bwd")) return -1;
+    if (bn_rows) *bn_rows = fuse ? ntiles : 0;
+    WgradReduceParams r;
+    memset(&r, 0, sizeof(r));
+    r.ws = (const float*)workspace; r.splits = wgs; r.Co = d->Cow ? d->Cow : d->Co; r.Co_pad = w.cop; r.Kpad = w.cip;
+    r.Ktot = d->Ci; r.fdC = make_fastdiv(d->Ci); r.dw = dw; r.Cw = d->Cw; r.taps = 1; r.slice4 = 0;
+    r.out_scale = out_scale; r.accumulate = zero_first ? 0 : 1;
+    const int64_t total = (int64_t)r.Co * r.Kpad / 4;
+    int lanes = 1;
+    while (lanes < 32 && lanes * 4 <= r.splits) lanes *= 2;
+    r.lanes = lanes;
+    hipLaunchKernelGGL(sf_wgrad_reduce_kernel, dim3(cdiv(total, SF_THREADS / lanes)), dim3(SF_THREADS), 0, s, r);
+    return check_launch("conv_c_bwd_reduce");
 }
 
 // ------------------------------------------------------------------------------------------------

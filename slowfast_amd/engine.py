@@ -498,19 +498,44 @@ class ConvUnit:
             return ops.conv_dgrad(dy, wd, geom, resid=resid, bn=(y, st.scale, st.shift))
         return ops.conv_dgrad(dy, wd, geom, resid=resid, resid_bits=resid_bits)
 
-    def bn_backward(self, dz, y, st, zmask=None, relu_self=False, want_g=False, part=None):
-        """BatchNorm3d backward (through ReLU) -> dy; writes bn.weight.grad / bn.bias.grad.  ``part``: partial sums already
-        taken by the producer of dz (backward(..., bn_fuse=...))."""
+    def _bn_grad_dest(self):
         bn = self.bn
         if bn.weight.requires_grad:
             dgamma, zg = _grad_dest(bn.weight)
             dbeta, zb = _grad_dest(bn.bias)
             assert zg == zb
-            accumulate = not zg
-        else:
-            dgamma = torch.empty_like(bn.weight)
-            dbeta = torch.empty_like(bn.bias)
-            accumulate = False
+            return dgamma, dbeta, not zg
+        return torch.empty_like(bn.weight), torch.empty_like(bn.bias), False
+
+    def fused_c_geom(self, x):
+        """The geometry of this unit on input ``x`` when the block-final BatchNorm backward can be fused into both of its gradients
+        (ops.conv_c_bwd: the library's planner accepts it, local BatchNorm statistics, a weight that wants its gradient), else None."""
+        if self.bn is None or _sync_of(self.bn) is not None or not self.conv.weight.requires_grad:
+            return None
+        geom = self.geom(x.shape)
+        return geom if ops.conv_c_bwd_plan(geom) is not None else None
+
+    def fused_c_backward(self, geom, x, dz, y, st, bits, part=None, bn_fuse=None):
+        """bn_backward(dz, y, st, zmask=bits, part=part) followed by backward(x, None, dy, need_dx=True, bn_fuse=bn_fuse) without the
+        gradient dy in memory: finalize (-> coef, bn.weight.grad / bn.bias.grad), then ONE launch for conv.weight.grad and d_in.
+        Returns (d_in, part of the inner BatchNorm or None)."""
+        bn = self.bn
+        dgamma, dbeta, accumulate = self._bn_grad_dest()
+        coef = ops.bn_bwd_coef(dz, y, bn.weight, st.mean, st.rstd, dgamma, dbeta, zmask=bits, inv_loss_scale=1.0,
+                               accumulate=accumulate, part=part)
+        dw, zero_first = _grad_dest(self.conv.weight)
+        _, wd = self.weights(geom)
+        fuse = None
+        if bn_fuse is not None:
+            y0, st0 = bn_fuse
+            fuse = (y0, st0.scale, st0.shift)
+        return ops.conv_c_bwd(dz, bits, y, coef, x, wd, geom, dw, bn=fuse, out_scale=1.0, zero_first=zero_first)
+
+    def bn_backward(self, dz, y, st, zmask=None, relu_self=False, want_g=False, part=None):
+        """BatchNorm3d backward (through ReLU) -> dy; writes bn.weight.grad / bn.bias.grad.  ``part``: partial sums already
+        taken by the producer of dz (backward(..., bn_fuse=...))."""
+        bn = self.bn
+        dgamma, dbeta, accumulate = self._bn_grad_dest()
         return ops.bn_bwd(dz, y, bn.weight, st.mean, st.rstd, dgamma, dbeta, zmask=zmask,
                           relu_affine=(st.scale, st.shift) if relu_self else None, inv_loss_scale=1.0,
                           accumulate=accumulate, want_g=want_g, sync=_sync_of(bn), part=part)
@@ -791,12 +816,18 @@ class ResBlockFn(torch.autograd.Function):
         part_c = tagged_bn_part(dout, raw[last])
         dout = as_cl(dout)
         need_dx = ctx.needs_input_grad[0]
-        dy = units[last].bn_backward(dout, raw[last], bn[last], zmask=bits, part=part_c)
+        # block-final BatchNorm backward fused into both gradients of conv c (ops.conv_c_bwd): dy_c is never written
+        cgeom = units[last].fused_c_geom(act[last - 1]) if last > 0 else None
+        if cgeom is None:
+            dy = units[last].bn_backward(dout, raw[last], bn[last], zmask=bits, part=part_c)
         if P is not None:
             dy1 = P.bn_backward(dout, y1, s1, zmask=bits)
         for i in range(last, 0, -1):
             part = None
-            if BN_FUSE_REDUCE and _sync_of(units[i - 1].bn) is None:
+            if i == last and cgeom is not None:
+                inner = (raw[i - 1], bn[i - 1]) if BN_FUSE_REDUCE and _sync_of(units[i - 1].bn) is None else None
+                d_in, part = units[i].fused_c_backward(cgeom, act[i - 1], dout, raw[i], bn[i], bits, part=part_c, bn_fuse=inner)
+            elif BN_FUSE_REDUCE and _sync_of(units[i - 1].bn) is None:
                 d_in, part = units[i].backward(act[i - 1], None, dy, need_dx=True, bn_fuse=(raw[i - 1], bn[i - 1]))
             else:
                 d_in = units[i].backward(act[i - 1], None, dy, need_dx=True)

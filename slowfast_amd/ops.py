@@ -5,7 +5,7 @@ shape (N, C, T, H, W) -- the reference's NCTHW convention (slowfast/models/video
 -- whose MEMORY order is N,T,H,W,C with a row pitch ``ld`` (``torch.channels_last_3d`` strides, or a
 channel slice of such a tensor).  Nothing in this file computes on the CPU or through ATen kernels.
 """
-from ctypes import byref, c_int32
+from ctypes import byref, c_int32, c_int64
 
 import torch
 
@@ -379,8 +379,10 @@ def bn_act(y, scale=None, shift=None, relu=False, resid=None, rscale=None, rshif
 
 
 def bn_bwd(dz, y, gamma, mean, rstd, dgamma, dbeta, zmask=None, relu_affine=None, inv_loss_scale=1.0,
-           accumulate=False, want_g=False, out=None, sync=None, part=None, sample_add=None):
+           accumulate=False, want_g=False, out=None, sync=None, part=None, sample_add=None, coef_only=False):
     """BatchNorm3d (training) backward through an optional ReLU.
+
+    ``coef_only``: stop after the finalize and return ``coef`` [3, C] (bn_bwd_coef; the apply pass is the caller's).
 
     dz: gradient w.r.t. act(bn(y)); the ReLU mask is ``zmask > 0`` (block output) or recomputed from
     ``relu_affine = (scale, shift)``; writes fp32 dgamma/dbeta and returns dy (and the masked g).
@@ -429,6 +431,8 @@ def bn_bwd(dz, y, gamma, mean, rstd, dgamma, dbeta, zmask=None, relu_affine=None
         lib.call("sf_bn_bwd_finalize", tot.data_ptr(), 1, C, gamma.numel(), float(M) * gsize, gamma.data_ptr(),
                  mean.data_ptr(), rstd.data_ptr(), float(inv_loss_scale), scratch[0].data_ptr(), scratch[1].data_ptr(), 0,
                  coef.data_ptr(), s)
+    if coef_only:
+        return coef
     dy = cl_empty(y.shape, y.device) if out is None else out
     if sample_add is not None:
         assert fused_part is not None and zmask is None and relu_affine is None and not want_g
@@ -441,6 +445,56 @@ def bn_bwd(dz, y, gamma, mean, rstd, dgamma, dbeta, zmask=None, relu_affine=None
              relu_self, coef.data_ptr(), dy.data_ptr(), cl_ld(dy), _ptr(g), cl_ld(g) if g is not None else 0, s,
              work=dict(bytes=2.0 * y.numel() * (3 + mcost + int(want_g))))
     return (dy, g) if want_g else dy
+
+
+def bn_bwd_coef(dz, y, gamma, mean, rstd, dgamma, dbeta, zmask=None, inv_loss_scale=1.0, accumulate=False, part=None):
+    """The first half of bn_bwd for an unsynchronised BatchNorm: the reduction pass (only when no ``part`` came in) and the
+    finalize -- dgamma / dbeta written, ``coef`` [3, C] returned (dy = k1 * g + k2 + k3 * y is then formed by conv_c_bwd)."""
+    return bn_bwd(dz, y, gamma, mean, rstd, dgamma, dbeta, zmask=zmask, inv_loss_scale=inv_loss_scale, accumulate=accumulate,
+                  part=part, coef_only=True)
+
+
+def conv_c_bwd_plan(geom, in_affine=False, mask_bits=True):
+    """(tile_rows, workspace_bytes) when sf_conv_c_bwd takes this geometry, else None (a function of the geometry alone).
+    The library reads the test hook SF_CBWD=0 (keep the three launches) on every call, so nothing is cached here."""
+    tile_rows, ws = c_int32(0), c_int64(0)
+    ok = get_lib().call("sf_conv_c_bwd_plan", byref(geom.desc(geom.Ci, geom.Co)), int(bool(in_affine)), int(bool(mask_bits)),
+                        byref(tile_rows), byref(ws))
+    return (tile_rows.value, ws.value) if ok == 1 else None
+
+
+def conv_c_bwd(dz, bits, yc, coef, act, wd, geom, dw, bn=None, out_scale=1.0, zero_first=True, out=None):
+    """Block-final BatchNorm backward fused into both gradients of the 1x1x1 convolution ``geom`` (sf_conv_c_bwd): from dz (gradient
+    w.r.t. the block output), its 1-bit ReLU mask ``bits``, the convolution's raw output ``yc``, ``coef`` (bn_bwd_coef) and input
+    ``act``: dw (+)= out_scale * dL/dw and d_in, without dy ever reaching memory.  ``bn = (y, scale, shift)`` of the BatchNorm-ReLU
+    that produced ``act``: also returns that BatchNorm's partial sums over the stored d_in, as conv_dgrad(..., bn=...) does.
+    Returns (d_in, part or None)."""
+    plan = conv_c_bwd_plan(geom)
+    assert plan is not None, "conv_c_bwd: the planner rejects this geometry"
+    tile_rows, ws_bytes = plan
+    assert tuple(act.shape) == geom.in_shape and tuple(dz.shape) == geom.out_shape and tuple(yc.shape) == geom.out_shape
+    assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == geom.Cow * geom.Cw * geom.taps
+    M = rows(yc)
+    assert bits.dtype == torch.uint8 and bits.is_contiguous() and bits.numel() == M * (geom.Co // 8)
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and tuple(coef.shape) == (3, geom.Co)
+    d_in = cl_empty(geom.in_shape, dz.device) if out is None else out
+    assert tuple(d_in.shape) == geom.in_shape
+    part, cap, nrows = None, 0, c_int32(0)
+    y0 = sc = sh = None
+    if bn is not None:
+        y0, sc, sh = bn
+        assert tuple(y0.shape) == geom.in_shape
+        cap = (M + tile_rows - 1) // tile_rows
+        part = torch.empty((cap, 2, geom.Ci), dtype=torch.float32, device=dz.device)
+    ws = _workspace(dz.device, ws_bytes)
+    W = 2.0 * M * geom.Co
+    get_lib().call("sf_conv_c_bwd", byref(geom.desc(cl_ld(act), geom.Co)), dz.data_ptr(), cl_ld(dz), bits.data_ptr(), yc.data_ptr(),
+                   cl_ld(yc), coef.data_ptr(), act.data_ptr(), wd.data_ptr(), _ptr(sc), _ptr(sh), _ptr(y0),
+                   cl_ld(y0) if y0 is not None else 0, _ptr(part), cap, byref(nrows), d_in.data_ptr(), cl_ld(d_in), dw.data_ptr(),
+                   float(out_scale), int(zero_first), ws.data_ptr(), ws.numel(), _stream(dz),
+                   work=dict(flops=4.0 * M * geom.Co * geom.Cw,
+                             bytes=W * (2 + 1 / 16) + 2.0 * M * geom.Ci * (2 + int(bn is not None))))
+    return d_in, (part[:nrows.value] if part is not None and nrows.value > 0 else None)
 
 
 # ------------------------------------------------------------------------------------------------

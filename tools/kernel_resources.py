@@ -33,8 +33,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--against", default=None, help="git revision to compare with")
     ap.add_argument("--md", default=None)
+    ap.add_argument("--filter", default=None, help="only kernels whose name contains this substring (e.g. sf_cbwd_kernel)")
     a = ap.parse_args()
     new = analyse(ROOT)
+    if a.filter:
+        new = {k: v for k, v in new.items() if a.filter in k}
     old = None
     if a.against:
         with tempfile.TemporaryDirectory() as tmp:

@@ -3,6 +3,7 @@
 Times conv fwd / dgrad / wgrad and the BN/elementwise kernels with HIP events on torch's current
 stream, prints achieved TFLOP/s and algorithmic GB/s per layer.  Usage:
     python tools/microbench.py [--batch 32] [--iters 5] [--json gpurun_out/microbench.json]
+    python tools/microbench.py --cbwd [--iters 7] [--json ...]    sf_conv_c_bwd against the three launches it replaces, HBM-cold
 """
 import argparse
 import json
@@ -61,6 +62,73 @@ def timeit(fn, iters):
 
 HBM_PEAK_GBS, MFMA_PEAK_TF = 8000.0, 2500.0
 
+# block-final convolutions that take sf_conv_c_bwd: (name, Ci, T, H, W, Co, blocks per step)
+CBWD_LAYERS = [
+    ("s2.slow c 64->256", 64, 8, 56, 56, 256, 3),
+    ("s2.fast c 8->32", 8, 32, 56, 56, 32, 3),
+    ("s3.fast c 16->64", 16, 32, 28, 28, 64, 4),
+    ("s4.fast c 32->128", 32, 32, 14, 14, 128, 6),
+    ("s5.fast c 64->256", 64, 32, 7, 7, 256, 3),
+]
+
+
+def time_cold(fn, iters, flush):
+    """HIP-event time of ONE launch sequence whose operands start in HBM: a write of `flush` (larger than the Infinity Cache)
+    precedes every timed call; the median of `iters` calls."""
+    fn()
+    times = []
+    for _ in range(iters):
+        flush.add_(1.0)
+        st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        st.record()
+        fn()
+        en.record()
+        torch.cuda.synchronize()
+        times.append(st.elapsed_time(en))
+    return sorted(times)[len(times) // 2]
+
+
+def cbwd_rows(batch, iters, dev, only=""):
+    """The fused launch (ops.conv_c_bwd: kernel + slab reduction) against the three it replaces (sf_bn_bwd_apply, sf_conv_wgrad,
+    sf_conv_dgrad_bn), HBM-cold, on the production shapes; W = bytes of the block-output tensor."""
+    from slowfast_amd.lib import get_lib
+    flush = torch.zeros(160 << 20, device=dev)                   # 640 MB of fp32
+    rows = []
+    for name, Ci, T, H, W, Co, cnt in CBWD_LAYERS:
+        if only and not any(f in name for f in only.split("|")):
+            continue
+        geom = ops.ConvGeom((batch, Ci, T, H, W), Co, (1, 1, 1))
+        assert ops.conv_c_bwd_plan(geom) is not None, name
+        act, yb = ops.cl_empty(geom.in_shape, dev), ops.cl_empty(geom.in_shape, dev)
+        dz, yc, dy = (ops.cl_empty(geom.out_shape, dev) for _ in range(3))
+        for t in (act, yb, dz, yc):
+            t.normal_()
+        M = geom.out_rows
+        bits = torch.randint(0, 256, (M, Co // 8), dtype=torch.uint8, device=dev)
+        w = torch.randn((Co, Ci, 1, 1, 1), device=dev) * 0.05
+        _, wd = ops.prep_weights(w, geom)
+        dw = torch.empty_like(w)
+        coef = torch.randn((3, Co), device=dev) * 0.1
+        sc, sh = torch.ones(Ci, device=dev), torch.zeros(Ci, device=dev)
+        lib, s = get_lib(), torch.cuda.current_stream(dev).cuda_stream
+
+        def apply():
+            lib.call("sf_bn_bwd_apply", M, Co, dz.data_ptr(), Co, bits.data_ptr(), 0, yc.data_ptr(), Co, None, None, 0,
+                     coef.data_ptr(), dy.data_ptr(), Co, None, 0, s)
+        t_fused = time_cold(lambda: ops.conv_c_bwd(dz, bits, yc, coef, act, wd, geom, dw, bn=(yb, sc, sh)), iters, flush)
+        t_apply = time_cold(apply, iters, flush)
+        t_wgrad = time_cold(lambda: ops.conv_wgrad(act, dy, geom, dw), iters, flush)
+        t_dgrad = time_cold(lambda: ops.conv_dgrad(dy, wd, geom, bn=(yb, sc, sh)), iters, flush)
+        Wb = 2.0 * M * Co
+        fused_bytes = Wb * (2 + 1 / 16) + 2.0 * M * Ci * 3
+        row = dict(name=name, count=cnt, W_MB=Wb / 1e6, fused_us=t_fused * 1e3, apply_us=t_apply * 1e3, wgrad_us=t_wgrad * 1e3,
+                   dgrad_bn_us=t_dgrad * 1e3, three_us=(t_apply + t_wgrad + t_dgrad) * 1e3, fused_gbs=fused_bytes / t_fused / 1e6)
+        rows.append(row)
+        print(f"{name:22s} x{cnt} W {row['W_MB']:6.1f} MB | fused {row['fused_us']:7.1f} us {row['fused_gbs']:6.0f} GB/s | apply "
+              f"{row['apply_us']:7.1f} + wgrad {row['wgrad_us']:7.1f} + dgrad_bn {row['dgrad_bn_us']:7.1f} = {row['three_us']:7.1f} us",
+              flush=True)
+    return rows
+
 
 def write_markdown(path, batch, rows, tot):
     """Per-geometry table: microseconds, algorithmic GB/s (operand + result bytes crossing HBM once), TFLOP/s and the
@@ -107,8 +175,17 @@ def main():
     ap.add_argument("--markers", action="store_true", help="launch a torch.arange kernel before the fwd / dgrad / wgrad phase of "
                     "every layer and after the last one: phase separators for tools/pmc_per_layer.py under rocprofv3 --pmc")
     ap.add_argument("--md", default="", help="write the per-geometry table (us, GB/s, TFLOP/s, roofline fraction) as markdown")
+    ap.add_argument("--cbwd", action="store_true", help="only the block-final fused backward (sf_conv_c_bwd) against the three "
+                    "launches it replaces, HBM-cold, on the production shapes")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.cbwd:
+        rows = cbwd_rows(a.batch, a.iters, dev, a.filter)
+        if a.json:
+            os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump(dict(batch=a.batch, cold=True, rows=rows), f, indent=1)
+        return
     rows = []
     tot = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0, "bn": 0.0}
     for name, Ci, T, H, W, Co, k, s, p, cnt in LAYERS:
