@@ -165,56 +165,33 @@ static bool igemm_glds_ok(const IgemmParams& p, bool pw) {
     return true;
 }
 
-template <int BN, int WM, int WN>
-static void launch_igemm(const IgemmParams& p, bool pw, hipStream_t s, int nbatch = 1) {
-    int mt = cdiv(p.M, 128);
-    dim3 grid((unsigned)(mt * p.ntiles_n), (unsigned)nbatch);
-    // 128-VGPR cap (4 workgroups per CU) for the 128-wide tile: +0.2..1.2 % end to end (profiles/r1_visit9_*_occ4.json);
-    // SF_IGEMM_OCC4=0 restores the uncapped build for A/B runs
-    static const bool occ4 = tune_knob("SF_IGEMM_OCC4", 1) != 0;
-    if (p.f32.out) {                // fp32 side rows of the output (sf_gemm_rows32: plain [M, K] operands)
-        if (igemm_glds_ok(p, pw)) hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, true, BN == 128, true>), grid, dim3(SF_THREADS), 0, s, p);
-        else hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, false, BN == 128, true>), grid, dim3(SF_THREADS), 0, s, p);
-        return;
-    }
-    if (igemm_glds_ok(p, pw)) {
-        hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, true, BN == 128>), grid, dim3(SF_THREADS), 0, s, p);
-        return;
-    }
-    constexpr bool kCap = BN == 128;        // 128-VGPR cap only matters (and is only compiled) for the 128-wide tile
-    const bool cap = kCap && occ4;
-    if (pw) {
-        if (cap) hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, false, kCap>), grid, dim3(SF_THREADS), 0, s, p);
-        else hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, false, false>), grid, dim3(SF_THREADS), 0, s, p);
-    } else {
-        if (cap) hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, false, false, kCap>), grid, dim3(SF_THREADS), 0, s, p);
-        else hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, false, false, false>), grid, dim3(SF_THREADS), 0, s, p);
-    }
-}
+// SF_TRACE is read on every call (a getenv per launch is noise): tests switch it on mid-process
+static inline bool sf_trace() { return test_hook("SF_TRACE", 0) != 0; }
 
 // ------------------------------------------------------------------------------------------------
-// Second-generation implicit GEMM (sf_igemm2.h): taken when the contraction is deep enough to pay for a 256-row tile
-// with a three-stage direct-to-LDS pipeline.  SF_IGEMM2=0 disables it, SF_IGEMM2_MINK sets the smallest K (default 512).
-template <int BN, int BK>
-static void launch_igemm2(Igemm2Params& q, hipStream_t s) {
-    q.ntiles_n = cdiv(q.Nout, BN);
-    const dim3 grid((unsigned)(cdiv(q.M, 256) * q.ntiles_n));
-    if constexpr (BN >= 64) {       // (N <= 32 never reaches this kernel: try_igemm2)
-        if (q.f32.out) { hipLaunchKernelGGL((sf_igemm2_kernel<256, BN, 4, 2, BK, 3, true>), grid, dim3(512), 0, s, q); return; }
-    }
-    hipLaunchKernelGGL((sf_igemm2_kernel<256, BN, 4, 2, BK, 3>), grid, dim3(512), 0, s, q);
-}
-// K step: 64 deep (48 KB stages, ONE 8-wave workgroup per CU) when the grid is at most ~one tile per CU anyway -- the
+// One plan per implicit-GEMM pass (convolution forward / data gradient, Linear, batched GEMM): plan_gemm alone decides, launch_gemm
+// launches what the plan says.  GEMM_GEN1: sf_igemm.h.  GEMM_GEN2: sf_igemm2.h, taken when the contraction is deep enough to pay for a
+// 256-row tile with a three-stage direct-to-LDS pipeline; SF_IGEMM2=0 disables it, SF_IGEMM2_MINK sets the smallest K (default 512).
+// GEMM_GEN2_CLASSES: that kernel, one launch per stride-residue class of a strided data gradient (igemm2_class).
+enum GemmKind { GEMM_GEN1, GEMM_GEN2, GEMM_GEN2_CLASSES };
+struct GemmPlan {
+    GemmKind kind;
+    bool pw;            // 1x1 taps with unit strides: rows are read without the gather
+    int nbatch;
+    int bn, bk;         // column tile 16 / 32 / 64 / 128; K step (second generation: 32 / 64, per class for GEMM_GEN2_CLASSES)
+    bool t128;          // second generation: the `linear` 128 x 128 tile (it always steps 32)
+    bool glds, cap;     // first generation: direct global -> LDS operand copies, 128-VGPR cap
+    bool rows32;        // the variant that also writes fp32 side rows (sf_gemm_rows32: plain [M, K] operands)
+    int bm;             // rows per M tile (= rows one bnb_part / column-sum row covers); 0 for the residue-class launches
+};
+// Second-generation K step and `linear` tile for M rows.  K step: 64 deep (48 KB stages, ONE 8-wave workgroup per CU) when the grid is at most ~one tile per CU anyway -- the
 // res5-sized layers; otherwise 32 deep (24 KB stages, TWO workgroups per CU: one tile's epilogue and pipeline fill hide
 // behind the other's K loop).  Measured per layer in profiles/r2/r2_v3_igemm2_variants.md.  SF_IGEMM2_BK=32|64 forces one.
-static void launch_igemm2_auto(Igemm2Params& q, hipStream_t s) {
-    const char* e;
-    const int tiles = cdiv(q.M, 256) * cdiv(q.Nout, q.Nout > 64 ? 128 : 64);
+static void plan_gemm2_tile(GemmPlan& g, const IgemmParams& p, int M) {
+    const int tiles = cdiv(M, 256) * cdiv(p.Nout, p.Nout > 64 ? 128 : 64);
     const int force_bk = tune_knob("SF_IGEMM2_BK", 0);
-    const bool bk64 = q.C % 64 == 0 && force_bk != 32 && (force_bk == 64 || tiles <= 320);
-    static const bool trace = test_hook("SF_TRACE", 0) != 0;
-    q.ablate = tune_knob("SF_IGEMM2_ABLATE", 0);        // diagnostic builds only: parts of the kernel switched off (wrong results)
-    if (trace) fprintf(stderr, "[sfamd] igemm2: M=%d N=%d C=%d taps=%d BK=%d omap=%d\n", q.M, q.Nout, q.C, q.ntaps, bk64 ? 64 : 32, q.omap);
+    const bool bk64 = p.g.C % 64 == 0 && force_bk != 32 && (force_bk == 64 || tiles <= 320);
+    g.bk = bk64 ? 64 : 32;
     // (256 x 256 tiles -- 128 flop per copied operand byte instead of 85, one workgroup per CU -- were measured in round 4 and
     // lost on both models: SlowFast 766.5 -> 741 clips/s on every eligible layer, 755 restricted to grids of >= 512 tiles,
     // MViTv2-S 590.9 -> 584 / 588; profiles/r4/r4_v6_knobs_ab.txt.  The same tile on a 16-wave workgroup (64 x 64 wave tiles, four
@@ -229,16 +206,7 @@ static void launch_igemm2_auto(Igemm2Params& q, hipStream_t s) {
     // 99.2 us HBM-cold, MViTv2-S 707 -> 712 clips/s (profiles/r5_v35_*).  Not below K = 512 (there the round-1 kernel at four
     // workgroups per CU stays ahead: 114 vs 128 us for fc1).
     const int t128 = test_hook("SF_IGEMM2_T128", 1);      // 2: also on grids of at most one round (tests)
-    if (t128 && q.linear && q.Nout > 64 && !q.stat_part && !q.bnb_part && (!bk64 || t128 == 2)) {
-        q.ntiles_n = cdiv(q.Nout, 128);
-        const dim3 grid((unsigned)(cdiv(q.M, 128) * q.ntiles_n));
-        if (q.f32.out) hipLaunchKernelGGL((sf_igemm2_kernel<128, 128, 2, 2, 32, 3, true>), grid, dim3(256), 0, s, q);
-        else hipLaunchKernelGGL((sf_igemm2_kernel<128, 128, 2, 2, 32, 3>), grid, dim3(256), 0, s, q);
-        return;
-    }
-    if (q.Nout > 64) { if (bk64) launch_igemm2<128, 64>(q, s); else launch_igemm2<128, 32>(q, s); }
-    else if (q.Nout > 32) { if (bk64) launch_igemm2<64, 64>(q, s); else launch_igemm2<64, 32>(q, s); }
-    else launch_igemm2<32, 32>(q, s);
+    g.t128 = t128 && p.linear && p.Nout > 64 && !p.stat_part && !p.bnb_part && (!bk64 || t128 == 2);
 }
 static bool igemm2_operands_ok(const IgemmParams& p, int nbatch) {
     const GatherSide& g = p.g;
@@ -264,19 +232,11 @@ static void igemm2_common(Igemm2Params& q, const IgemmParams& p) {
     q.bnb_bits = p.bnb_bits;
     q.f32 = p.f32;
     q.linear = p.linear;
+    q.ablate = tune_knob("SF_IGEMM2_ABLATE", 0);        // diagnostic builds only: parts of the kernel switched off (wrong results)
 }
-static bool try_igemm2(const IgemmParams& p, hipStream_t s, int nbatch = 1) {
-    // read on every call (three getenv per launch are noise): tests lower the thresholds for single cases
-    const char* e;
-    const bool off = test_hook("SF_IGEMM2", 1) == 0;
-    const int mink = test_hook("SF_IGEMM2_MINK", 512);
-    const int minrows = test_hook("SF_IGEMM2_MINROWS", 4096);
+// GEMM_GEN2: every row, every tap
+static void igemm2_dense(Igemm2Params& q, const IgemmParams& p) {
     const GatherSide& g = p.g;
-    if (off || !igemm2_operands_ok(p, nbatch)) return false;
-    if (g.Ktot < mink || p.Nout <= 32 || p.M < minrows) return false;
-    if (g.mode == 1 && !(g.strT == 1 && g.strH == 1 && g.strW == 1)) return false;
-    const int taps = g.kT * g.kH * g.kW;
-    Igemm2Params q;
     igemm2_common(q, p);
     q.fdrW = g.fdrW; q.fdrH = g.fdrH; q.fdrT = g.fdrT;
     const int sgn = g.mode == 0 ? 1 : -1;
@@ -287,7 +247,7 @@ static bool try_igemm2(const IgemmParams& p, hipStream_t s, int nbatch = 1) {
         q.mulT = q.mulH = q.mulW = 1;
         q.offT = g.padT; q.offH = g.padH; q.offW = g.padW;
     }
-    q.ntaps = taps;
+    q.ntaps = g.kT * g.kH * g.kW;
     int t = 0;
     for (int kt = 0; kt < g.kT; ++kt)
         for (int kh = 0; kh < g.kH; ++kh)
@@ -298,8 +258,6 @@ static bool try_igemm2(const IgemmParams& p, hipStream_t s, int nbatch = 1) {
                 q.taps[t].wcol = t * g.C;
             }
     q.M = p.M;
-    launch_igemm2_auto(q, s);
-    return true;
 }
 
 // Strided data gradient as sub-convolutions (reference op: the backward of nn.Conv3d with stride > 1 -- ResBlock.branch1
@@ -310,87 +268,158 @@ static bool try_igemm2(const IgemmParams& p, hipStream_t s, int nbatch = 1) {
 // per class: no all-padding K steps (a 3x3 stride-2 convolution wastes 3/4 of them in the gather formulation, a strided
 // 1x1 shortcut 3/4 of its ROWS), every tap of a step real, wave-uniform and direct-to-LDS.  Classes without any tap
 // (1x1 kernels) just store the residual / zeros.
-static bool try_igemm2_strided_dgrad(const IgemmParams& p, hipStream_t s) {
-    const char* e;
-    const bool off = test_hook("SF_IGEMM2", 1) == 0 || tune_knob("SF_IGEMM2_STRIDED", 1) == 0;
-    const int minrows = test_hook("SF_IGEMM2_MINROWS", 4096);
+// GEMM_GEN2_CLASSES: the launch of residue class r; false when the class holds no input position
+static bool igemm2_class(Igemm2Params& q, const IgemmParams& p, const int r[3]) {
     const GatherSide& g = p.g;
-    if (off || g.mode != 1 || (g.strT == 1 && g.strH == 1 && g.strW == 1)) return false;
-    if (!igemm2_operands_ok(p, 1) || p.Nout <= 16 || p.M < minrows || p.stat_part || p.act_mode) return false;
     const int Ti = (int)g.fdrT.d, Hi = (int)g.fdrH.d, Wi = (int)g.fdrW.d;      // rows = input positions
     const int N = p.M / (Ti * Hi * Wi);
     const int str[3] = {g.strT, g.strH, g.strW}, pad[3] = {g.padT, g.padH, g.padW}, dil[3] = {g.dilT, g.dilH, g.dilW};
     const int ker[3] = {g.kT, g.kH, g.kW}, ext[3] = {Ti, Hi, Wi};
-    for (int rt = 0; rt < str[0]; ++rt)
-        for (int rh = 0; rh < str[1]; ++rh)
-            for (int rw = 0; rw < str[2]; ++rw) {
-                const int r[3] = {rt, rh, rw};
-                int q0[3], cnt[3];
-                bool empty = false;
+    int q0[3], cnt[3];
+    for (int a = 0; a < 3; ++a) {
+        const int num = pad[a] - r[a];
+        q0[a] = num > 0 ? (num + str[a] - 1) / str[a] : 0;
+        const int top = ext[a] - 1 + pad[a] - r[a];
+        const int q1 = top >= 0 ? top / str[a] : -1;
+        cnt[a] = q1 - q0[a] + 1;
+        if (cnt[a] <= 0) return false;
+    }
+    igemm2_common(q, p);
+    q.fdrT = make_fastdiv(cnt[0]); q.fdrH = make_fastdiv(cnt[1]); q.fdrW = make_fastdiv(cnt[2]);
+    q.mulT = q.mulH = q.mulW = 1;
+    q.offT = q0[0]; q.offH = q0[1]; q.offW = q0[2];
+    int nt = 0, tap = 0;
+    for (int kt = 0; kt < ker[0]; ++kt)
+        for (int kh = 0; kh < ker[1]; ++kh)
+            for (int kw = 0; kw < ker[2]; ++kw, ++tap) {
+                const int k[3] = {kt, kh, kw};
+                int d[3];
+                bool ok = true;
                 for (int a = 0; a < 3; ++a) {
-                    const int num = pad[a] - r[a];
-                    q0[a] = num > 0 ? (num + str[a] - 1) / str[a] : 0;
-                    const int top = ext[a] - 1 + pad[a] - r[a];
-                    const int q1 = top >= 0 ? top / str[a] : -1;
-                    cnt[a] = q1 - q0[a] + 1;
-                    if (cnt[a] <= 0) empty = true;
+                    const int v = r[a] - k[a] * dil[a];
+                    if (v % str[a] != 0) { ok = false; break; }
+                    d[a] = v / str[a];
                 }
-                if (empty) continue;
-                Igemm2Params q;
-                igemm2_common(q, p);
-                q.fdrT = make_fastdiv(cnt[0]); q.fdrH = make_fastdiv(cnt[1]); q.fdrW = make_fastdiv(cnt[2]);
-                q.mulT = q.mulH = q.mulW = 1;
-                q.offT = q0[0]; q.offH = q0[1]; q.offW = q0[2];
-                int nt = 0, tap = 0;
-                for (int kt = 0; kt < ker[0]; ++kt)
-                    for (int kh = 0; kh < ker[1]; ++kh)
-                        for (int kw = 0; kw < ker[2]; ++kw, ++tap) {
-                            const int k[3] = {kt, kh, kw};
-                            int d[3];
-                            bool ok = true;
-                            for (int a = 0; a < 3; ++a) {
-                                const int v = r[a] - k[a] * dil[a];
-                                if (v % str[a] != 0) { ok = false; break; }
-                                d[a] = v / str[a];
-                            }
-                            if (!ok) continue;
-                            q.dt[nt] = (int8_t)d[0]; q.dh[nt] = (int8_t)d[1]; q.dw[nt] = (int8_t)d[2];
-                            q.taps[nt].dlin = (d[0] * g.sH + d[1]) * g.sW + d[2];
-                            q.taps[nt].wcol = tap * g.C;
-                            ++nt;
-                        }
-                q.ntaps = nt;
-                q.M = N * cnt[0] * cnt[1] * cnt[2];
-                q.omap = 1;
-                q.oT = Ti; q.oH = Hi; q.oW = Wi;
-                q.omT = str[0]; q.omH = str[1]; q.omW = str[2];
-                q.ooT = str[0] * q0[0] + r[0] - pad[0]; q.ooH = str[1] * q0[1] + r[1] - pad[1]; q.ooW = str[2] * q0[2] + r[2] - pad[2];
-                launch_igemm2_auto(q, s);
+                if (!ok) continue;
+                q.dt[nt] = (int8_t)d[0]; q.dh[nt] = (int8_t)d[1]; q.dw[nt] = (int8_t)d[2];
+                q.taps[nt].dlin = (d[0] * g.sH + d[1]) * g.sW + d[2];
+                q.taps[nt].wcol = tap * g.C;
+                ++nt;
             }
+    q.ntaps = nt;
+    q.M = N * cnt[0] * cnt[1] * cnt[2];
+    q.omap = 1;
+    q.oT = Ti; q.oH = Hi; q.oW = Wi;
+    q.omT = str[0]; q.omH = str[1]; q.omW = str[2];
+    q.ooT = str[0] * q0[0] + r[0] - pad[0]; q.ooH = str[1] * q0[1] + r[1] - pad[1]; q.ooW = str[2] * q0[2] + r[2] - pad[2];
     return true;
 }
 
-// bm_used: rows per M tile of the kernel that ran (= rows one bnb_part row covers); 0 for the residue-class launches
-static int run_igemm(IgemmParams& p, bool pw, hipStream_t s, int* bm_used = nullptr) {
-    if (bm_used) *bm_used = 256;
-    if (try_igemm2(p, s)) return check_launch("igemm2");
-    if (bm_used) *bm_used = 0;
-    if (try_igemm2_strided_dgrad(p, s)) return check_launch("igemm2 strided dgrad");
-    if (bm_used) *bm_used = 128;
-    if (p.Nout > 64) { p.ntiles_n = cdiv(p.Nout, 128); launch_igemm<128, 64, 64>(p, pw, s); }
-    else if (p.Nout > 32) { p.ntiles_n = 1; launch_igemm<64, 32, 64>(p, pw, s); }
-    else if (p.Nout > 16) { p.ntiles_n = 1; launch_igemm<32, 32, 32>(p, pw, s); }
-    else { p.ntiles_n = 1; launch_igemm<16, 32, 16>(p, pw, s); }
-    return check_launch("igemm");
+static GemmPlan plan_gemm(const IgemmParams& p, bool pointwise, int nbatch) {
+    GemmPlan g;
+    memset(&g, 0, sizeof(g));
+    g.pw = pointwise; g.nbatch = nbatch; g.rows32 = p.f32.out != nullptr;
+    g.bn = p.Nout > 64 ? 128 : p.Nout > 32 ? 64 : p.Nout > 16 ? 32 : 16;   // the second generation has no 16, and 32 for residue classes only
+    // hooks are read on every call (a few getenv per launch are noise): tests lower the thresholds for single cases
+    const bool gen2 = test_hook("SF_IGEMM2", 1) != 0 && p.M >= test_hook("SF_IGEMM2_MINROWS", 4096) && igemm2_operands_ok(p, nbatch);
+    const bool unit = p.g.strT == 1 && p.g.strH == 1 && p.g.strW == 1;
+    if (gen2 && p.g.Ktot >= test_hook("SF_IGEMM2_MINK", 512) && p.Nout > 32 && (p.g.mode == 0 || unit)) {
+        g.kind = GEMM_GEN2;
+        plan_gemm2_tile(g, p, p.M);
+        g.bm = g.t128 ? 128 : 256;
+        return g;
+    }
+    if (gen2 && tune_knob("SF_IGEMM2_STRIDED", 1) != 0 && p.g.mode == 1 && !unit && p.Nout > 16 && !p.stat_part && !p.act_mode) {
+        g.kind = GEMM_GEN2_CLASSES;     // bk: launch_gemm, per class; bm stays 0
+        return g;
+    }
+    g.kind = GEMM_GEN1;
+    g.bk = 32; g.bm = 128;
+    g.glds = igemm_glds_ok(p, pointwise);
+    // 128-VGPR cap (4 workgroups per CU) for the 128-wide tile: +0.2..1.2 % end to end (profiles/r1_visit9_*_occ4.json);
+    // SF_IGEMM_OCC4=0 restores the uncapped build for A/B runs (the direct-to-LDS and side-row variants exist capped only)
+    static const bool occ4 = tune_knob("SF_IGEMM_OCC4", 1) != 0;
+    g.cap = g.bn == 128 && (occ4 || g.glds || g.rows32);
+    return g;
+}
+
+template <int BN, int WM, int WN>
+static void launch_igemm(const GemmPlan& g, IgemmParams& p, hipStream_t s) {
+    p.ntiles_n = cdiv(p.Nout, BN);
+    const dim3 grid((unsigned)(cdiv(p.M, 128) * p.ntiles_n), (unsigned)g.nbatch), block(SF_THREADS);
+    constexpr bool kCap = BN == 128;        // 128-VGPR cap only matters (and is only compiled) for the 128-wide tile
+    if (g.rows32) {
+        if (g.glds) hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, true, kCap, true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, false, kCap, true>), grid, block, 0, s, p);
+    } else if (g.glds) {
+        hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, true, kCap>), grid, block, 0, s, p);
+    } else if (g.pw) {
+        if (g.cap) hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, false, kCap>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, true, false, false>), grid, block, 0, s, p);
+    } else {
+        if (g.cap) hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, false, false, kCap>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((sf_igemm_kernel<BN, WM, WN, false, false, false>), grid, block, 0, s, p);
+    }
+}
+template <int BM, int BN, int BK>           // 256 x BN tiles on 4 x 2 waves, 128 x 128 on 2 x 2
+static void launch_igemm2(const GemmPlan& g, Igemm2Params& q, hipStream_t s) {
+    constexpr int WM = BM / 64;
+    q.ntiles_n = cdiv(q.Nout, BN);
+    const dim3 grid((unsigned)(cdiv(q.M, BM) * q.ntiles_n)), block(WM * 128);
+    if constexpr (BN >= 64) {       // (N <= 32 never reaches this kernel densely: plan_gemm)
+        if (g.rows32) { hipLaunchKernelGGL((sf_igemm2_kernel<BM, BN, WM, 2, BK, 3, true>), grid, block, 0, s, q); return; }
+    }
+    hipLaunchKernelGGL((sf_igemm2_kernel<BM, BN, WM, 2, BK, 3>), grid, block, 0, s, q);
+}
+static void launch_gemm2(const GemmPlan& g, Igemm2Params& q, hipStream_t s) {
+    if (sf_trace()) fprintf(stderr, "[sfamd] igemm2: M=%d N=%d C=%d taps=%d BK=%d omap=%d\n", q.M, q.Nout, q.C, q.ntaps, g.bk, q.omap);
+    if (g.t128) launch_igemm2<128, 128, 32>(g, q, s);
+    else if (g.bn == 128) { if (g.bk == 64) launch_igemm2<256, 128, 64>(g, q, s); else launch_igemm2<256, 128, 32>(g, q, s); }
+    else if (g.bn == 64) { if (g.bk == 64) launch_igemm2<256, 64, 64>(g, q, s); else launch_igemm2<256, 64, 32>(g, q, s); }
+    else launch_igemm2<256, 32, 32>(g, q, s);
+}
+// The one switch over the kernel instantiations of the family (p.ntiles_n is the launcher's to write)
+static void launch_gemm(const GemmPlan& g, IgemmParams& p, hipStream_t s) {
+    Igemm2Params q;
+    switch (g.kind) {
+    case GEMM_GEN2: igemm2_dense(q, p); launch_gemm2(g, q, s); return;
+    case GEMM_GEN2_CLASSES:
+        for (int rt = 0; rt < p.g.strT; ++rt)
+            for (int rh = 0; rh < p.g.strH; ++rh)
+                for (int rw = 0; rw < p.g.strW; ++rw) {
+                    const int r[3] = {rt, rh, rw};
+                    if (!igemm2_class(q, p, r)) continue;
+                    GemmPlan gc = g;
+                    plan_gemm2_tile(gc, p, q.M);
+                    launch_gemm2(gc, q, s);
+                }
+        return;
+    case GEMM_GEN1:
+        if (g.bn == 128) launch_igemm<128, 64, 64>(g, p, s);
+        else if (g.bn == 64) launch_igemm<64, 32, 64>(g, p, s);
+        else if (g.bn == 32) launch_igemm<32, 32, 32>(g, p, s);
+        else launch_igemm<16, 32, 16>(g, p, s);
+        return;
+    }
+}
+// plan + launch of a convolution pass; the plan goes back to callers that need the rows per M tile
+static int run_igemm(IgemmParams& p, bool pw, hipStream_t s, GemmPlan* plan = nullptr) {
+    const GemmPlan g = plan_gemm(p, pw, 1);
+    if (plan) *plan = g;
+    launch_gemm(g, p, s);
+    return check_launch(g.kind == GEMM_GEN2 ? "igemm2" : g.kind == GEMM_GEN2_CLASSES ? "igemm2 strided dgrad" : "igemm");
 }
 
 // ------------------------------------------------------------------------------------------------
 // LDS-patch direct convolution for the thin W-pair-folded stems (sf_stem.h); SF_STEM_GENERIC=1 keeps the implicit GEMM.
+enum StemFwd { STEM_FWD_GENERIC, STEM_FWD_SMALL_GENERIC, STEM_FWD_SMALL_ROWS_1_3, STEM_FWD_ROWS_2_7, STEM_FWD_SLIDE };
 struct StemPlan {
     bool ok, thin3, small;      // small: the patch fits SF_STEM_CHUNKS_SMALL (12 KiB of LDS instead of 52)
     int tiles_w, tiles_h, tiles_t, ntiles, F, PR;
     int wg_blocks, tiles_per_block, Kpad, wgroups;
     size_t ws_bytes;
+    StemFwd fwd;                // plan_stem_fwd: the forward kernel variant ...
+    int seg_groups;             // ... and, for STEM_FWD_SLIDE, the groups of 4 output frames one workgroup walks
 };
 static StemPlan plan_stem(const sf_conv_desc* d) {
     StemPlan s;
@@ -432,29 +461,41 @@ static StemPlan plan_stem(const sf_conv_desc* d) {
 // SF_STEM_SLIDE (test hook, read per call): groups of 4 output frames a workgroup of the sliding Fast-stem forward walks; 0 = the
 // tile kernel.  profiles/r6_v34_stem_slide_ab.txt
 #define SF_STEM_SLIDE_GROUPS 4
-// patch-row-major variants for the two shapes that matter (row stride / kernel height compile-time), generic loop otherwise;
-// SF_STEM_ROWMAJOR=0 keeps the generic loop for A/B runs
-#define SF_STEM_FWD_LAUNCH(sp, q, stream)                                                                                          \
-    do {                                                                                                                          \
-        static const bool rm_ = tune_knob("SF_STEM_ROWMAJOR", 1) != 0;                           \
-        const dim3 g_((sp).ntiles), b_(SF_THREADS);                                                                               \
-        const int sg_ = test_hook("SF_STEM_SLIDE", SF_STEM_SLIDE_GROUPS);                                                         \
-        if (rm_ && sg_ > 0 && (q).sH == 2 && (q).kH == 7 && !(sp).small && (q).sT == 1 && (q).kT > 1 && (q).kT <= 5 &&            \
-            (q).Co <= 8 && !(q).bnb_y) {                                                                                                         \
-            StemParams qs_ = (q);                   /* a workgroup walks sg_ groups of 4 output frames (sf_stem_fwd_slide_kernel) */ \
-            qs_.seg_groups = sg_ < (sp).tiles_t ? sg_ : (sp).tiles_t;                                                             \
-            qs_.tiles_t = cdiv((sp).tiles_t, qs_.seg_groups);                                                                     \
-            qs_.fd_tt = make_fastdiv(qs_.tiles_t);                                                                                \
-            const dim3 gs_((unsigned)((int64_t)(q).N * qs_.tiles_t * (sp).tiles_h * (sp).tiles_w));                                \
-            if (test_hook("SF_TRACE", 0)) fprintf(stderr, "[sfamd] stem_fwd_slide: %u runs of %d groups\n", gs_.x, qs_.seg_groups); \
-            hipLaunchKernelGGL((sf_stem_fwd_slide_kernel<2, 7>), gs_, b_, 0, (hipStream_t)(stream), qs_);                         \
-        } else if (rm_ && (q).sH == 2 && (q).kH == 7 && !(sp).small)                                                              \
-            hipLaunchKernelGGL((sf_stem_fwd_kernel<SF_STEM_CHUNKS, 2, 7>), g_, b_, 0, (hipStream_t)(stream), q);                  \
-        else if (rm_ && (q).sH == 1 && (q).kH == 3 && (sp).small)                                                                 \
-            hipLaunchKernelGGL((sf_stem_fwd_kernel<SF_STEM_CHUNKS_SMALL, 1, 3>), g_, b_, 0, (hipStream_t)(stream), q);            \
-        else if ((sp).small) hipLaunchKernelGGL((sf_stem_fwd_kernel<SF_STEM_CHUNKS_SMALL>), g_, b_, 0, (hipStream_t)(stream), q); \
-        else hipLaunchKernelGGL((sf_stem_fwd_kernel<SF_STEM_CHUNKS>), g_, b_, 0, (hipStream_t)(stream), q);                       \
-    } while (0)
+// The direct convolution as a forward-shaped pass (forward, fused forward, thin3 data gradient): plan_stem plus the kernel variant.
+// !ok, the implicit GEMM runs: d is no stem (no thin3 layer with `thin3_only`), or the tiles outnumber the `table_rows` rows of the
+// partial table they fill (`table`: statistics or the fused BatchNorm-backward sums, `bnb`).  Variants: patch-row-major for the two
+// shapes that matter (row stride / kernel height compile-time), generic loop otherwise; SF_STEM_ROWMAJOR=0 keeps the generic loop
+static StemPlan plan_stem_fwd(const sf_conv_desc* d, bool thin3_only, bool table, int table_rows, bool bnb) {
+    StemPlan s = plan_stem(d);
+    if (!s.ok || (thin3_only && !s.thin3) || (table && s.ntiles > table_rows)) { s.ok = false; return s; }
+    static const bool rm = tune_knob("SF_STEM_ROWMAJOR", 1) != 0;
+    const int sg = test_hook("SF_STEM_SLIDE", SF_STEM_SLIDE_GROUPS);
+    const bool rows_2_7 = rm && d->sH == 2 && d->kH == 7 && !s.small;
+    if (rows_2_7 && sg > 0 && d->sT == 1 && d->kT > 1 && d->kT <= 5 && d->Co <= 8 && !bnb) {
+        s.fwd = STEM_FWD_SLIDE;
+        s.seg_groups = sg < s.tiles_t ? sg : s.tiles_t;
+    } else if (rows_2_7) s.fwd = STEM_FWD_ROWS_2_7;
+    else if (rm && d->sH == 1 && d->kH == 3 && s.small) s.fwd = STEM_FWD_SMALL_ROWS_1_3;
+    else s.fwd = s.small ? STEM_FWD_SMALL_GENERIC : STEM_FWD_GENERIC;
+    return s;
+}
+static void launch_stem_fwd(const StemPlan& sp, const StemParams& q, hipStream_t s) {
+    const dim3 g(sp.ntiles), b(SF_THREADS);
+    switch (sp.fwd) {
+    case STEM_FWD_SLIDE: {
+        StemParams qs = q;                   // a workgroup walks seg_groups groups of 4 output frames (sf_stem_fwd_slide_kernel)
+        qs.seg_groups = sp.seg_groups; qs.tiles_t = cdiv(sp.tiles_t, qs.seg_groups); qs.fd_tt = make_fastdiv(qs.tiles_t);
+        const dim3 gs((unsigned)((int64_t)q.N * qs.tiles_t * sp.tiles_h * sp.tiles_w));
+        if (sf_trace()) fprintf(stderr, "[sfamd] stem_fwd_slide: %u runs of %d groups\n", gs.x, qs.seg_groups);
+        hipLaunchKernelGGL((sf_stem_fwd_slide_kernel<2, 7>), gs, b, 0, s, qs);
+        return;
+    }
+    case STEM_FWD_ROWS_2_7: hipLaunchKernelGGL((sf_stem_fwd_kernel<SF_STEM_CHUNKS, 2, 7>), g, b, 0, s, q); return;
+    case STEM_FWD_SMALL_ROWS_1_3: hipLaunchKernelGGL((sf_stem_fwd_kernel<SF_STEM_CHUNKS_SMALL, 1, 3>), g, b, 0, s, q); return;
+    case STEM_FWD_SMALL_GENERIC: hipLaunchKernelGGL((sf_stem_fwd_kernel<SF_STEM_CHUNKS_SMALL>), g, b, 0, s, q); return;
+    case STEM_FWD_GENERIC: hipLaunchKernelGGL((sf_stem_fwd_kernel<SF_STEM_CHUNKS>), g, b, 0, s, q); return;
+    }
+}
 static StemParams stem_params(const sf_conv_desc* d, const StemPlan& s, const void* x) {
     StemParams p;
     memset(&p, 0, sizeof(p));
@@ -471,6 +512,21 @@ static StemParams stem_params(const sf_conv_desc* d, const StemPlan& s, const vo
     p.F = s.F; p.PR = s.PR;
     p.fd_pc = make_fastdiv(SF_STEM_PC); p.fd_prpc = make_fastdiv(s.PR * SF_STEM_PC);
     p.Kpad = s.Kpad; p.tiles_per_block = s.tiles_per_block; p.wgroups = s.wgroups;
+    return p;
+}
+static StemParams stem_fwd_params(const sf_conv_desc* d, const StemPlan& s, const void* x, const void* w, int ldw, void* y) {
+    StemParams p = stem_params(d, s, x);
+    p.wmat = (const f16*)w; p.ldw = ldw; p.y = (f16*)y;
+    return p;
+}
+// the operands every implicit-GEMM pass has: gathered rows x packed weights -> 16-bit rows, optional bias and residual
+static IgemmParams gemm_params(const GatherSide& g, int M, const void* w, int ldw, int Nout, void* y, int ldy,
+                               const float* bias, const void* resid, int ldr) {
+    IgemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.g = g; p.M = M; p.ksteps = cdiv(g.Ktot, 32);
+    p.wmat = (const f16*)w; p.ldw = ldw; p.Nout = Nout; p.y = (f16*)y; p.ldy = ldy;
+    p.bias = bias; p.resid = (const f16*)resid; p.ldr = ldr;
     return p;
 }
 
@@ -541,30 +597,20 @@ extern "C" int sf_conv_fwd(const sf_conv_desc* d, const void* x, const void* wf,
     REQUIRE(x && wf && y, "sf_conv_fwd: null pointer");
     REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "sf_conv_fwd: in_scale/in_shift must come together");
     REQUIRE(!in_scale || d->Ci <= 512, "sf_conv_fwd: fused input BatchNorm supports Ci <= 512 (got %d)", d->Ci);
+    int32_t ldf, ldd;
+    sf_conv_weight_ld(d, &ldf, &ldd);
     if (!in_scale && !bias) {
-        const StemPlan sp = plan_stem(d);
-        if (sp.ok && (!stat_part || sp.ntiles <= sf_conv_fwd_mtiles(d))) {
-            StemParams q = stem_params(d, sp, x);
-            int32_t ldf0, ldd0;
-            sf_conv_weight_ld(d, &ldf0, &ldd0);
-            q.wmat = (const f16*)wf; q.ldw = ldf0; q.y = (f16*)y;
+        const StemPlan sp = plan_stem_fwd(d, false, stat_part != nullptr, sf_conv_fwd_mtiles(d), false);
+        if (sp.ok) {
+            StemParams q = stem_fwd_params(d, sp, x, wf, ldf, y);
             q.stat_part = stat_part; q.stat_rows = sf_conv_fwd_mtiles(d);
-            const bool trace = test_hook("SF_TRACE", 0) != 0;          // read per call: tests switch it on mid-process
-            if (trace) fprintf(stderr, "[sfamd] stem_fwd: %d tiles, patch %dx%dx%d chunks\n", sp.ntiles, sp.F, sp.PR, SF_STEM_PC);
-            SF_STEM_FWD_LAUNCH(sp, q, stream);
+            if (sf_trace()) fprintf(stderr, "[sfamd] stem_fwd: %d tiles, patch %dx%dx%d chunks\n", sp.ntiles, sp.F, sp.PR, SF_STEM_PC);
+            launch_stem_fwd(sp, q, (hipStream_t)stream);
             return check_launch("stem_fwd");
         }
     }
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.g = gather_fwd(d, x, in_scale, in_shift, in_relu);
-    p.M = d->N * d->To * d->Ho * d->Wo;
-    int32_t ldf, ldd;
-    sf_conv_weight_ld(d, &ldf, &ldd);
-    p.wmat = (const f16*)wf; p.ldw = ldf; p.Nout = d->Co;
-    p.ksteps = cdiv(p.g.Ktot, 32);
-    p.y = (f16*)y; p.ldy = d->ldy;
-    p.bias = bias; p.resid = nullptr; p.ldr = 0;
+    IgemmParams p = gemm_params(gather_fwd(d, x, in_scale, in_shift, in_relu), d->N * d->To * d->Ho * d->Wo, wf, ldf, d->Co,
+                                y, d->ldy, bias, nullptr, 0);
     p.stat_part = stat_part;
     return run_igemm(p, is_pointwise(d), (hipStream_t)stream);
 }
@@ -574,28 +620,19 @@ extern "C" int sf_conv_fwd_fused(const sf_conv_desc* d, const void* x, const voi
     if (check_desc(d)) return -1;
     REQUIRE(x && wf && y, "sf_conv_fwd_fused: null pointer");
     REQUIRE(!resid || (ldr >= d->Co && ldr % 8 == 0), "sf_conv_fwd_fused: bad residual pitch");
+    int32_t ldf, ldd;
+    sf_conv_weight_ld(d, &ldf, &ldd);
     if (!resid) {        // thin W-pair-folded stems: the LDS-patch direct convolution with bias / ReLU in its epilogue
-        const StemPlan sp = plan_stem(d);
+        const StemPlan sp = plan_stem_fwd(d, false, false, 0, false);
         if (sp.ok) {
-            StemParams q = stem_params(d, sp, x);
-            int32_t ldf0, ldd0;
-            sf_conv_weight_ld(d, &ldf0, &ldd0);
-            q.wmat = (const f16*)wf; q.ldw = ldf0; q.y = (f16*)y;
+            StemParams q = stem_fwd_params(d, sp, x, wf, ldf, y);
             q.bias = bias; q.out_relu = out_relu;
-            SF_STEM_FWD_LAUNCH(sp, q, stream);
+            launch_stem_fwd(sp, q, (hipStream_t)stream);
             return check_launch("stem_fwd_fused");
         }
     }
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.g = gather_fwd(d, x, nullptr, nullptr, 0);
-    p.M = d->N * d->To * d->Ho * d->Wo;
-    int32_t ldf, ldd;
-    sf_conv_weight_ld(d, &ldf, &ldd);
-    p.wmat = (const f16*)wf; p.ldw = ldf; p.Nout = d->Co;
-    p.ksteps = cdiv(p.g.Ktot, 32);
-    p.y = (f16*)y; p.ldy = d->ldy;
-    p.bias = bias; p.resid = (const f16*)resid; p.ldr = ldr;
+    IgemmParams p = gemm_params(gather_fwd(d, x, nullptr, nullptr, 0), d->N * d->To * d->Ho * d->Wo, wf, ldf, d->Co,
+                                y, d->ldy, bias, resid, ldr);
     p.act_mode = out_relu ? 3 : 0;
     return run_igemm(p, is_pointwise(d), (hipStream_t)stream);
 }
@@ -609,16 +646,9 @@ static int conv_dgrad_impl(const sf_conv_desc* d, const void* dy, const void* wd
     if (check_desc(d)) return -1;
     REQUIRE(dy && wd && dx, "sf_conv_dgrad: null pointer");
     REQUIRE(!resid || (ldr >= d->Ci && ldr % 8 == 0), "sf_conv_dgrad: bad residual pitch");
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.g = gather_dgrad(d, dy);
-    p.M = d->N * d->Ti * d->Hi * d->Wi;
     int32_t ldf, ldd;
     sf_conv_weight_ld(d, &ldf, &ldd);
-    p.wmat = (const f16*)wd; p.ldw = ldd; p.Nout = d->Ci;
-    p.ksteps = cdiv(p.g.Ktot, 32);
-    p.y = (f16*)dx; p.ldy = d->ldx;
-    p.resid = (const f16*)resid; p.ldr = ldr;
+    IgemmParams p = gemm_params(gather_dgrad(d, dy), d->N * d->Ti * d->Hi * d->Wi, wd, ldd, d->Ci, dx, d->ldx, nullptr, resid, ldr);
     REQUIRE(!resid_bits || resid, "sf_conv_dgrad: resid_bits without a residual");
     p.resid_bits = (const uint8_t*)resid_bits;
     // the fused BatchNorm-backward reduction rides on dense stride-1 data gradients only (a strided one runs as one launch
@@ -631,18 +661,17 @@ static int conv_dgrad_impl(const sf_conv_desc* d, const void* dy, const void* wd
         dd.Ci = d->Co; dd.Cw = d->Co; dd.Co = d->Ci; dd.Cow = 0;
         dd.pT = d->kT - 1 - d->pT; dd.pH = d->kH - 1 - d->pH; dd.pW = d->kW - 1 - d->pW;
         dd.ldx = d->ldy; dd.ldy = d->ldx;
-        const StemPlan sp = plan_stem(&dd);
-        if (sp.ok && sp.thin3 && (!fuse || sp.ntiles <= cdiv(p.M, 128))) {
-            StemParams q = stem_params(&dd, sp, dy);
+        const StemPlan sp = plan_stem_fwd(&dd, true, fuse, cdiv(p.M, 128), fuse);
+        if (sp.ok) {
+            StemParams q = stem_fwd_params(&dd, sp, dy, wd, ldd, dx);
             const int S = d->kT * d->kH;
-            q.wmat = (const f16*)wd; q.ldw = ldd; q.y = (f16*)dx;
             q.wo0 = ((S - 1) * 3 + 2) * 8; q.wos = -24; q.wog = -8; q.kwc = 3;
             if (fuse) {
                 q.bnb_y = (const f16*)bn->y0; q.bnb_ld = bn->ld0; q.bnb_scale = bn->scale; q.bnb_shift = bn->shift;
                 q.bnb_bits = (const uint8_t*)bn->bits;
                 q.stat_part = bn->part0; q.stat_rows = 0;
             }
-            SF_STEM_FWD_LAUNCH(sp, q, stream);
+            launch_stem_fwd(sp, q, (hipStream_t)stream);
             if (bn_rows) *bn_rows = fuse ? sp.ntiles : 0;
             return check_launch("stem_dgrad");
         }
@@ -651,9 +680,9 @@ static int conv_dgrad_impl(const sf_conv_desc* d, const void* dy, const void* wd
         p.bnb_y = (const f16*)bn->y0; p.bnb_ld = bn->ld0; p.bnb_part = bn->part0;
         p.bnb_scale = bn->scale; p.bnb_shift = bn->shift; p.bnb_bits = (const uint8_t*)bn->bits;
     }
-    int bm = 0;
-    const int rc = run_igemm(p, is_pointwise(d), (hipStream_t)stream, &bm);
-    if (bn_rows) *bn_rows = (fuse && bm > 0) ? cdiv(p.M, bm) : 0;
+    GemmPlan g;
+    const int rc = run_igemm(p, is_pointwise(d), (hipStream_t)stream, &g);
+    if (bn_rows) *bn_rows = (fuse && g.bm > 0) ? cdiv(p.M, g.bm) : 0;
     return rc;
 }
 
@@ -675,27 +704,57 @@ extern "C" int sf_conv_dgrad_bn(const sf_conv_desc* d, const void* dy, const voi
     return conv_dgrad_impl(d, dy, wd, resid, ldr, resid_bits, dx, &bn, bn_rows, stream);
 }
 
-template <int BMW, int WM, int WN, int KS>
-static void launch_wgrad(WgradParams& p, dim3 grid3, hipStream_t s) {
+// First-generation weight-gradient tiles (sf_conv_wgrad, sf_bgemm_tn): output rows in tiles of BMW, KS 32-position chunks per stage
+static inline int wgrad1_bmw(int rows) { return rows >= 128 ? 128 : rows >= 64 ? 64 : rows >= 32 ? 32 : 16; }
+static inline int wgrad1_ks(int bmw) { return bmw <= 32 ? 4 : 1; }
+static void launch_wgrad1(int bmw, WgradParams& p, dim3 grid3, hipStream_t s) {
     p.tiles_k = grid3.x; p.tiles_c = grid3.y;
-    const dim3 grid(grid3.x * grid3.y * grid3.z);
-    hipLaunchKernelGGL((sf_wgrad_kernel<BMW, WM, WN, KS>), grid, dim3(SF_THREADS), 0, s, p);
+    const dim3 grid(grid3.x * grid3.y * grid3.z), block(SF_THREADS);
+    switch (bmw) {
+        case 128: hipLaunchKernelGGL((sf_wgrad_kernel<128, 64, 64, 1>), grid, block, 0, s, p); break;
+        case 64: hipLaunchKernelGGL((sf_wgrad_kernel<64, 32, 64, 1>), grid, block, 0, s, p); break;
+        case 32: hipLaunchKernelGGL((sf_wgrad_kernel<32, 32, 32, 4>), grid, block, 0, s, p); break;
+        default: hipLaunchKernelGGL((sf_wgrad_kernel<16, 16, 32, 4>), grid, block, 0, s, p); break;
+    }
+}
+// sums `slabs` partial tile sets of [Co_pad][Kpad] into dw: ~>= 4 per lane, 8..256 element quads per block
+static void launch_wgrad_reduce(const sf_conv_desc* d, const float* ws, int slabs, int Co_pad, int Kpad, bool slice4, float* dw,
+                                float out_scale, int zero_first, hipStream_t s) {
+    WgradReduceParams r;
+    memset(&r, 0, sizeof(r));
+    r.ws = ws; r.splits = slabs; r.Co = d->Cow ? d->Cow : d->Co; r.Co_pad = Co_pad; r.Kpad = Kpad;
+    r.taps = d->kT * d->kH * d->kW; r.Ktot = r.taps * d->Ci; r.fdC = make_fastdiv(d->Ci); r.dw = dw; r.Cw = d->Cw;
+    if (slice4) { r.slice4 = 1; r.Ktot = d->kT * d->kH * 32; }      // thin3 stems: 4-chunk slices, the 4th is no tap
+    r.out_scale = out_scale; r.accumulate = zero_first ? 0 : 1;
+    const int64_t total = (int64_t)r.Co * r.Kpad / 4;
+    r.lanes = 1;
+    while (r.lanes < 32 && r.lanes * 4 <= r.splits) r.lanes *= 2;
+    hipLaunchKernelGGL(sf_wgrad_reduce_kernel, dim3(cdiv(total, SF_THREADS / r.lanes)), dim3(SF_THREADS), 0, s, r);
 }
 
-// Split-K plan of the weight gradient: the reduction over the M = N*To*Ho*Wo positions is cut into `splits`
-// slabs so that ~4 workgroups per CU are in flight; each split stores its [Co_pad][Kpad] fp32 partial tile
-// set with plain stores and sf_wgrad_reduce_kernel sums them (deterministic, no atomics).
+// One plan per weight gradient: the path that runs with its tiles, splits, padded extents and workspace.  Every path cuts the
+// reduction over the M = N*To*Ho*Wo positions into splits; each stores fp32 partial tile sets ("slabs" of [Co_pad][Kpad]) with
+// plain stores and sf_wgrad_reduce_kernel sums them (deterministic, no atomics).
+enum WgradPath { WGRAD_GEN1, WGRAD_ROWTAB, WGRAD_STEM };
 struct WgradPlan {
-    int BMW, KS, tiles_k, tiles_c, Co_pad, Kpad, nchunks, chunks_per_split, splits;
-    size_t ws_bytes;
+    WgradPath path;
+    bool thin, dual;                    // WGRAD_ROWTAB: sf_wgrad2t_kernel / two splits per workgroup; neither: one split per workgroup
+    int BMW, BKW, KS, tiles_k, tiles_c, Co_pad, Kpad;
+    int nchunks, chunks_per_split;      // WGRAD_GEN1: 32-position chunks
+    int rows_per_split, splits;         // (rows: WGRAD_ROWTAB)
+    int slabs;                          // fp32 partial tile sets written (= splits, or split PAIRS of the dual kernel)
+    size_t tab_bytes, ws_bytes;         // row table at the head of the workspace (WGRAD_ROWTAB); everything
+    StemPlan stem;                      // plan_stem(d), evaluated once (WGRAD_STEM launches from it)
 };
-static WgradPlan plan_wgrad(const sf_conv_desc* d) {
+// WGRAD_GEN1 (sf_wgrad_kernel): ~4 workgroups per CU in flight
+static WgradPlan plan_wgrad1(const sf_conv_desc* d) {
     WgradPlan w;
+    memset(&w, 0, sizeof(w));
+    w.path = WGRAD_GEN1;
     const int taps = d->kT * d->kH * d->kW;
     const int Ktot = taps * d->Ci;
     const int64_t M = (int64_t)d->N * d->To * d->Ho * d->Wo;
-    w.BMW = d->Co >= 128 ? 128 : d->Co >= 64 ? 64 : d->Co >= 32 ? 32 : 16;
-    w.KS = w.BMW <= 32 ? 4 : 1;                          // 32-position chunks per pipeline stage
+    w.BMW = wgrad1_bmw(d->Co); w.KS = wgrad1_ks(w.BMW);
     w.tiles_k = cdiv(Ktot, 128);
     w.tiles_c = cdiv(d->Co, w.BMW);
     w.Kpad = w.tiles_k * 128;
@@ -711,23 +770,15 @@ static WgradPlan plan_wgrad(const sf_conv_desc* d) {
     if (splits < 1) splits = 1;
     w.chunks_per_split = cdiv(nstages, splits) * w.KS;   // whole stages per split
     w.splits = cdiv(w.nchunks, w.chunks_per_split);
+    w.slabs = w.splits;
     w.ws_bytes = (size_t)slab * w.splits;
     return w;
 }
 
-// Second-generation weight gradient (sf_wgrad2.h): plain (already activated) input, at least 33 output channels, a K axis
-// that fills most of a 256-wide tile.  SF_WGRAD2=0 keeps the first kernel.
-struct Wgrad2Plan {
-    bool ok, thin, dual;
-    int BMW, BKW, tiles_k, tiles_c, Co_pad, Kpad, rows_per_split, splits;
-    int slabs;          // fp32 partial tiles sets written (= splits, or split PAIRS of the dual kernel)
-    size_t tab_bytes, ws_bytes;
-};
-static Wgrad2Plan plan_wgrad2(const sf_conv_desc* d) {
-    Wgrad2Plan w;
-    memset(&w, 0, sizeof(w));
-    const char* e;
-    if (test_hook("SF_WGRAD2", 1) == 0) return w;
+// WGRAD_ROWTAB, the second-generation weight gradient (sf_wgrad2.h): plain (already activated) input, no stem, at least 33 output
+// channels, a K axis that fills most of a 256-wide tile.  SF_WGRAD2=0 keeps the first kernel.  False: w is untouched.
+static bool plan_wgrad2(const sf_conv_desc* d, WgradPlan& w) {
+    if (test_hook("SF_WGRAD2", 1) == 0) return false;
     const int mink = test_hook("SF_WGRAD2_MINK", 192);
     const int minrows = test_hook("SF_WGRAD2_MINROWS", 4096);
     const int taps = d->kT * d->kH * d->kW;
@@ -736,17 +787,15 @@ static Wgrad2Plan plan_wgrad2(const sf_conv_desc* d) {
     // (s4.slow b: 120 us at 522 workgroups, 99 us at 396; profiles/r3/r3_v2_wgrad_sweep.md -- which also records a one-workgroup-
     // per-CU six-stage ring with half the splits losing on every layer; that variant is gone again, commit 4267b0c has it).
     const int target = test_hook("SF_WGRAD2_BLOCKS", 512);
-    (void)taps;
     const int Ktot = taps * d->Ci;
     const int64_t M = (int64_t)d->N * d->To * d->Ho * d->Wo;
-    if (taps > SF_I2_MAXTAPS || M < minrows) return w;
-    if ((d->kT - 1) * d->dT > 127 || (d->kH - 1) * d->dH > 127 || (d->kW - 1) * d->dW > 127) return w;
-    if (plan_stem(d).ok) return w;
+    if (taps > SF_I2_MAXTAPS || M < minrows) return false;
+    if ((d->kT - 1) * d->dT > 127 || (d->kH - 1) * d->dH > 127 || (d->kW - 1) * d->dW > 127) return false;
     if (d->Co <= 32) {
         // thin layers (sf_wgrad2t_kernel): one workgroup tile holds every output channel; SF_WGRAD2T=0 keeps the first kernel
-        if (test_hook("SF_WGRAD2T", 1) == 0) return w;
+        if (test_hook("SF_WGRAD2T", 1) == 0) return false;
         const int minrows_t = test_hook("SF_WGRAD2T_MINROWS", 16384);
-        if (M < minrows_t) return w;
+        if (M < minrows_t) return false;
         w.thin = true;
         w.BMW = d->Co <= 16 ? 16 : 32;
         w.BKW = Ktot <= 32 ? 32 : 128;
@@ -764,10 +813,10 @@ static Wgrad2Plan plan_wgrad2(const sf_conv_desc* d) {
         w.tab_bytes = ((size_t)M * 8 + 255) / 256 * 256 + 1280;  // pad: the thin kernel reads whole 32-byte groups up to one 128-position stage past M
         w.ws_bytes = w.tab_bytes + (size_t)w.Co_pad * w.Kpad * 4 * w.splits;
         w.slabs = w.splits;
-        w.ok = true;
-        return w;
+        w.path = WGRAD_ROWTAB;
+        return true;
     }
-    if (Ktot < mink) return w;
+    if (Ktot < mink) return false;
     w.BMW = d->Co > 64 ? 128 : 64;       // 64-row co-tiles for wide layers lose 20-40 % on res3-res5 (profiles/r3/r3_final_wgrad_sweep.md)
     w.tiles_k = cdiv(Ktot, 256);
     w.tiles_c = cdiv(d->Co, w.BMW);
@@ -802,7 +851,21 @@ static Wgrad2Plan plan_wgrad2(const sf_conv_desc* d) {
     w.slabs = w.dual ? cdiv(w.splits, 2) : w.splits;
     w.tab_bytes = ((size_t)M * 8 + 255) / 256 * 256 + 1280;  // pad: the thin kernel reads whole 32-byte groups up to one 128-position stage past M
     w.ws_bytes = w.tab_bytes + (size_t)slab * w.splits;
-    w.ok = true;
+    w.path = WGRAD_ROWTAB;
+    return true;
+}
+// The path sf_conv_wgrad takes: the row-table kernel, else the direct-convolution stem kernel (both read a plain input: a fused
+// input BatchNorm, `in_affine`, keeps the first generation), else the first generation.
+static WgradPlan plan_conv_wgrad(const sf_conv_desc* d, bool in_affine) {
+    const StemPlan sp = plan_stem(d);
+    WgradPlan w;
+    memset(&w, 0, sizeof(w));
+    if (in_affine || !(sp.ok || plan_wgrad2(d, w))) w = plan_wgrad1(d);
+    else if (sp.ok) {
+        w.path = WGRAD_STEM;
+        w.slabs = sp.wg_blocks * sp.wgroups; w.Co_pad = 16; w.Kpad = sp.Kpad; w.ws_bytes = sp.ws_bytes;
+    }
+    w.stem = sp;
     return w;
 }
 
@@ -828,25 +891,22 @@ static void launch_rowtab(const sf_conv_desc* d, void* tab, hipStream_t s) {
 
 extern "C" int64_t sf_conv_wgrad_rowtab_bytes(const sf_conv_desc* d) {
     if (check_desc(d)) return -1;
-    const Wgrad2Plan w2 = plan_wgrad2(d);
-    return w2.ok ? (int64_t)w2.tab_bytes : 0;
+    return (int64_t)plan_conv_wgrad(d, false).tab_bytes;
 }
 
 extern "C" int sf_conv_wgrad_rowtab(const sf_conv_desc* d, void* tab, sf_stream_t stream) {
     if (check_desc(d)) return -1;
     REQUIRE(tab && (uintptr_t)tab % 16 == 0, "sf_conv_wgrad_rowtab: tab must be a 16-byte aligned device pointer");
-    REQUIRE(plan_wgrad2(d).ok, "sf_conv_wgrad_rowtab: this geometry does not take the row-table kernel (sf_conv_wgrad_rowtab_bytes == 0)");
+    REQUIRE(plan_conv_wgrad(d, false).path == WGRAD_ROWTAB, "sf_conv_wgrad_rowtab: this geometry does not take the row-table kernel (sf_conv_wgrad_rowtab_bytes == 0)");
     launch_rowtab(d, tab, (hipStream_t)stream);
     return check_launch("wgrad_rowtab");
 }
 
 extern "C" int64_t sf_conv_wgrad_workspace(const sf_conv_desc* d) {
     if (check_desc(d)) return -1;
-    int64_t generic = (int64_t)plan_wgrad(d).ws_bytes;
-    const Wgrad2Plan w2 = plan_wgrad2(d);
-    if (w2.ok && (int64_t)w2.ws_bytes > generic) generic = (int64_t)w2.ws_bytes;
-    const StemPlan sp = plan_stem(d);
-    return sp.ok && (int64_t)sp.ws_bytes > generic ? (int64_t)sp.ws_bytes : generic;
+    // the larger of the two paths the geometry can take: callers keep one value per geometry, with or without a fused input BatchNorm
+    const int64_t plain = (int64_t)plan_conv_wgrad(d, false).ws_bytes, affine = (int64_t)plan_conv_wgrad(d, true).ws_bytes;
+    return plain > affine ? plain : affine;
 }
 
 extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* in_scale, const float* in_shift,
@@ -857,14 +917,12 @@ extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* 
     REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "sf_conv_wgrad: in_scale/in_shift must come together");
     REQUIRE(!in_scale || d->Ci <= 512, "sf_conv_wgrad: fused input BatchNorm supports Ci <= 512 (got %d)", d->Ci);
     hipStream_t s = (hipStream_t)stream;
-    int splits, Co_pad, Kpad;
     GatherSide gk = gather_fwd(d, x, in_scale, in_shift, in_relu);
-    const StemPlan sp = plan_stem(d);
-    const Wgrad2Plan w2 = in_scale ? Wgrad2Plan{} : plan_wgrad2(d);
-    float* slabs = (float*)workspace;
-    if (w2.ok) {
-        REQUIRE(workspace_bytes >= (int64_t)w2.ws_bytes, "sf_conv_wgrad: workspace too small (%lld < %lld bytes)",
-                (long long)workspace_bytes, (long long)w2.ws_bytes);
+    const WgradPlan w = plan_conv_wgrad(d, in_scale != nullptr);
+    REQUIRE(workspace_bytes >= (int64_t)w.ws_bytes, "sf_conv_wgrad: workspace too small (%lld < %lld bytes)",
+            (long long)workspace_bytes, (long long)w.ws_bytes);
+    float* slabs = (float*)((char*)workspace + w.tab_bytes);
+    if (w.path == WGRAD_ROWTAB) {
         REQUIRE(((uintptr_t)x | (uintptr_t)dy | (uintptr_t)workspace) % 16 == 0, "sf_conv_wgrad: operands must be 16-byte aligned");
         Wgrad2Params q;
         memset(&q, 0, sizeof(q));
@@ -878,45 +936,37 @@ extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* 
         q.dy = (const f16*)dy; q.ldy = d->ldy; q.Co = d->Co;
         q.M = d->N * d->To * d->Ho * d->Wo; q.Ktot = gk.Ktot;
         q.rowtab = (const i32x2*)(rowtab ? rowtab : workspace);
-        slabs = (float*)((char*)workspace + w2.tab_bytes);
-        q.ws = slabs; q.Co_pad = w2.Co_pad; q.Kpad = w2.Kpad;
-        q.tiles_k = w2.tiles_k; q.tiles_c = w2.tiles_c; q.rows_per_split = w2.rows_per_split;
-        q.stage_stride = (w2.thin && tune_knob("SF_WGRAD2T_RR", 1) != 0) ? w2.splits : 0;
-        const dim3 grid((unsigned)(w2.tiles_k * w2.tiles_c * w2.slabs));
-        static const bool trace = test_hook("SF_TRACE", 0) != 0;
-        if (trace) fprintf(stderr, "[sfamd] wgrad2: M=%d Co=%d K=%d tiles %dx%d splits %d%s\n", q.M, q.Co, q.Ktot, w2.tiles_c, w2.tiles_k, w2.splits,
-                           w2.dual ? " (two per workgroup)" : "");
-        if (w2.thin) {
-            if (w2.BMW == 16 && w2.BKW == 128) hipLaunchKernelGGL((sf_wgrad2t_kernel<16, 128, 2>), grid, dim3(256), 0, s, q);
-            else if (w2.BMW == 32 && w2.BKW == 128) hipLaunchKernelGGL((sf_wgrad2t_kernel<32, 128, 2>), grid, dim3(256), 0, s, q);
-            else if (w2.BMW == 16) hipLaunchKernelGGL((sf_wgrad2t_kernel<16, 32, 3>), grid, dim3(256), 0, s, q);
+        q.ws = slabs; q.Co_pad = w.Co_pad; q.Kpad = w.Kpad;
+        q.tiles_k = w.tiles_k; q.tiles_c = w.tiles_c; q.rows_per_split = w.rows_per_split;
+        q.stage_stride = (w.thin && tune_knob("SF_WGRAD2T_RR", 1) != 0) ? w.splits : 0;
+        const dim3 grid((unsigned)(w.tiles_k * w.tiles_c * w.slabs));
+        if (sf_trace()) fprintf(stderr, "[sfamd] wgrad2: M=%d Co=%d K=%d tiles %dx%d splits %d%s\n", q.M, q.Co, q.Ktot, w.tiles_c, w.tiles_k, w.splits,
+                                w.dual ? " (two per workgroup)" : "");
+        if (w.thin) {
+            if (w.BMW == 16 && w.BKW == 128) hipLaunchKernelGGL((sf_wgrad2t_kernel<16, 128, 2>), grid, dim3(256), 0, s, q);
+            else if (w.BMW == 32 && w.BKW == 128) hipLaunchKernelGGL((sf_wgrad2t_kernel<32, 128, 2>), grid, dim3(256), 0, s, q);
+            else if (w.BMW == 16) hipLaunchKernelGGL((sf_wgrad2t_kernel<16, 32, 3>), grid, dim3(256), 0, s, q);
             else hipLaunchKernelGGL((sf_wgrad2t_kernel<32, 32, 3>), grid, dim3(256), 0, s, q);
-        } else if (w2.dual) {
-            if (w2.BMW == 128) hipLaunchKernelGGL((sf_wgrad2_kernel<128, true>), grid, dim3(1024), 0, s, q);
+        } else if (w.dual) {
+            if (w.BMW == 128) hipLaunchKernelGGL((sf_wgrad2_kernel<128, true>), grid, dim3(1024), 0, s, q);
             else hipLaunchKernelGGL((sf_wgrad2_kernel<64, true>), grid, dim3(1024), 0, s, q);
         } else {
-            if (w2.BMW == 128) hipLaunchKernelGGL((sf_wgrad2_kernel<128>), grid, dim3(512), 0, s, q);
+            if (w.BMW == 128) hipLaunchKernelGGL((sf_wgrad2_kernel<128>), grid, dim3(512), 0, s, q);
             else hipLaunchKernelGGL((sf_wgrad2_kernel<64>), grid, dim3(512), 0, s, q);
         }
-        splits = w2.slabs; Co_pad = w2.Co_pad; Kpad = w2.Kpad;
-    } else if (sp.ok && !in_scale) {
-        REQUIRE(workspace_bytes >= (int64_t)sp.ws_bytes, "sf_conv_wgrad: workspace too small (%lld < %lld bytes)",
-                (long long)workspace_bytes, (long long)sp.ws_bytes);
+    } else if (w.path == WGRAD_STEM) {
+        const StemPlan& sp = w.stem;
         StemParams q = stem_params(d, sp, x);
         q.dy = (const f16*)dy; q.ws = (float*)workspace;
-        const bool trace = test_hook("SF_TRACE", 0) != 0;          // read per call: tests switch it on mid-process
-        if (trace) fprintf(stderr, "[sfamd] stem_wgrad: %d workgroups x %d tiles\n", sp.wg_blocks, sp.tiles_per_block);
+        if (sf_trace()) fprintf(stderr, "[sfamd] stem_wgrad: %d workgroups x %d tiles\n", sp.wg_blocks, sp.tiles_per_block);
         static const bool stem_plain = tune_knob("SF_STEM_XCD", 1) == 0;
         q.plain_order = stem_plain ? 1 : 0;
-        if (d->Co <= 8 && sp.small) hipLaunchKernelGGL((sf_stem_wgrad_kernel<8, SF_STEM_CHUNKS_SMALL>), dim3(sp.wg_blocks), dim3(SF_STEM_WG_THREADS), 0, s, q);
-        else if (d->Co <= 8) hipLaunchKernelGGL((sf_stem_wgrad_kernel<8, SF_STEM_CHUNKS>), dim3(sp.wg_blocks), dim3(SF_STEM_WG_THREADS), 0, s, q);
-        else if (sp.small) hipLaunchKernelGGL((sf_stem_wgrad_kernel<16, SF_STEM_CHUNKS_SMALL>), dim3(sp.wg_blocks), dim3(SF_STEM_WG_THREADS), 0, s, q);
-        else hipLaunchKernelGGL((sf_stem_wgrad_kernel<16, SF_STEM_CHUNKS>), dim3(sp.wg_blocks), dim3(SF_STEM_WG_THREADS), 0, s, q);
-        splits = sp.wg_blocks * sp.wgroups; Co_pad = 16; Kpad = sp.Kpad;
+        const dim3 grid(sp.wg_blocks), block(SF_STEM_WG_THREADS);
+        if (d->Co <= 8 && sp.small) hipLaunchKernelGGL((sf_stem_wgrad_kernel<8, SF_STEM_CHUNKS_SMALL>), grid, block, 0, s, q);
+        else if (d->Co <= 8) hipLaunchKernelGGL((sf_stem_wgrad_kernel<8, SF_STEM_CHUNKS>), grid, block, 0, s, q);
+        else if (sp.small) hipLaunchKernelGGL((sf_stem_wgrad_kernel<16, SF_STEM_CHUNKS_SMALL>), grid, block, 0, s, q);
+        else hipLaunchKernelGGL((sf_stem_wgrad_kernel<16, SF_STEM_CHUNKS>), grid, block, 0, s, q);
     } else {
-        const WgradPlan w = plan_wgrad(d);
-        REQUIRE(workspace_bytes >= (int64_t)w.ws_bytes, "sf_conv_wgrad: workspace too small (%lld < %lld bytes)",
-                (long long)workspace_bytes, (long long)w.ws_bytes);
         REQUIRE(w.splits <= 65535, "sf_conv_wgrad: too many splits");
         WgradParams p;
         memset(&p, 0, sizeof(p));
@@ -925,28 +975,10 @@ extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* 
         p.M = d->N * d->To * d->Ho * d->Wo;
         p.ws = (float*)workspace; p.Co_pad = w.Co_pad; p.Kpad = w.Kpad;
         p.nchunks = w.nchunks; p.chunks_per_split = w.chunks_per_split;
-        dim3 grid(w.tiles_k, w.tiles_c, w.splits);
-        switch (w.BMW) {
-            case 128: launch_wgrad<128, 64, 64, 1>(p, grid, s); break;
-            case 64: launch_wgrad<64, 32, 64, 1>(p, grid, s); break;
-            case 32: launch_wgrad<32, 32, 32, 4>(p, grid, s); break;
-            default: launch_wgrad<16, 16, 32, 4>(p, grid, s); break;
-        }
-        splits = w.splits; Co_pad = w.Co_pad; Kpad = w.Kpad;
+        launch_wgrad1(w.BMW, p, dim3(w.tiles_k, w.tiles_c, w.splits), s);
     }
     if (check_launch("wgrad")) return -1;
-    WgradReduceParams r;
-    r.ws = slabs; r.splits = splits; r.Co = d->Cow ? d->Cow : d->Co; r.Co_pad = Co_pad; r.Kpad = Kpad;
-    r.Ktot = gk.Ktot; r.fdC = gk.fdC; r.dw = dw; r.Cw = d->Cw; r.taps = d->kT * d->kH * d->kW;
-    r.slice4 = 0;
-    if (sp.ok && sp.thin3 && !in_scale && !w2.ok) { r.slice4 = 1; r.Ktot = d->kT * d->kH * 32; }   // 4-chunk slices, the 4th is no tap
-    r.out_scale = out_scale; r.accumulate = zero_first ? 0 : 1;
-    int64_t total = (int64_t)r.Co * Kpad / 4;              // element quads
-    int lanes = 1;
-    while (lanes < 32 && lanes * 4 <= splits) lanes *= 2;   // ~>= 4 splits per lane, 8..256 elements per block
-    r.lanes = lanes;
-    const int per_block = SF_THREADS / lanes;
-    hipLaunchKernelGGL(sf_wgrad_reduce_kernel, dim3(cdiv(total, per_block)), dim3(SF_THREADS), 0, s, r);
+    launch_wgrad_reduce(d, slabs, w.slabs, w.Co_pad, w.Kpad, w.path == WGRAD_STEM && w.stem.thin3, dw, out_scale, zero_first, s);
     return check_launch("wgrad_reduce");
 }
 
@@ -955,7 +987,7 @@ extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* 
 // 1x1x1, unit stride, unpadded, Ci % 8 == 0 <= 64, Co % 32 == 0 <= 256, a plain (already activated) input and the bit-mask form of
 // the block-output ReLU -- never the row count, so that small test models take the production path.  SF_CBWD=0 (test hook) keeps the
 // three launches; SF_CBWD_WGS (test hook) sets the workgroup count so that a small tensor makes every workgroup walk several tiles.
-// The rows are dealt to the workgroups exactly as sf_conv_wgrad deals them to its splits (plan_wgrad: contiguous runs of 32-row
+// The rows are dealt to the workgroups exactly as sf_conv_wgrad deals them to its splits (plan_wgrad1: contiguous runs of 32-row
 // chunks; plan_wgrad2's thin kernel: 128-row stages round robin, the four waves a quarter each), every 32-row MFMA step lands on the
 // accumulator it lands on there and the slabs meet in the same sf_wgrad_reduce_kernel launch: dw has the bits of the three-launch
 // path.  The inner BatchNorm's table keeps the 128-row tiles and the per-thread order of the data gradient's epilogue.
@@ -1044,16 +1076,16 @@ extern "C" int sf_conv_c_bwd(const sf_conv_desc* d, const void* dz, int32_t lddz
     p.dx = (f16*)d_in; p.lddx = ld_in; p.ws = (float*)workspace; p.tiles128 = ntiles;
     // who sums which rows: as the weight gradient of the three-launch path would (see above)
     int wgs;
-    const Wgrad2Plan w2 = plan_wgrad2(d);
+    const WgradPlan w2 = plan_conv_wgrad(d, false);
     const int forced = test_hook("SF_CBWD_WGS", 0);
     if (forced > 0) {
         wgs = forced < SF_CBWD_MAX_WGS ? forced : SF_CBWD_MAX_WGS;
         p.rps = roundup(cdiv(M, wgs), 32);
         wgs = cdiv(M, p.rps);
-    } else if (w2.ok && w2.thin && w2.splits <= SF_CBWD_MAX_WGS) {
+    } else if (w2.path == WGRAD_ROWTAB && w2.thin && w2.splits <= SF_CBWD_MAX_WGS) {
         wgs = w2.splits; p.rps = 0;
     } else {
-        const WgradPlan w1 = plan_wgrad(d);
+        const WgradPlan w1 = plan_wgrad1(d);
         wgs = w1.splits; p.rps = w1.chunks_per_split * 32;
         REQUIRE(wgs <= SF_CBWD_MAX_WGS, "sf_conv_c_bwd: %d splits", wgs);
     }
@@ -1061,16 +1093,7 @@ extern "C" int sf_conv_c_bwd(const sf_conv_desc* d, const void* dz, int32_t lddz
     SF_CBWD_FOR_SHAPE(w.cip, w.cop, hipLaunchKernelGGL((sf_cbwd_kernel<CIP_, COP_>), dim3(wgs), dim3(SF_THREADS), 0, s, p));
     if (check_launch("conv_c_bwd")) return -1;
     if (bn_rows) *bn_rows = fuse ? ntiles : 0;
-    WgradReduceParams r;
-    memset(&r, 0, sizeof(r));
-    r.ws = (const float*)workspace; r.splits = wgs; r.Co = d->Cow ? d->Cow : d->Co; r.Co_pad = w.cop; r.Kpad = w.cip;
-    r.Ktot = d->Ci; r.fdC = make_fastdiv(d->Ci); r.dw = dw; r.Cw = d->Cw; r.taps = 1; r.slice4 = 0;
-    r.out_scale = out_scale; r.accumulate = zero_first ? 0 : 1;
-    const int64_t total = (int64_t)r.Co * r.Kpad / 4;
-    int lanes = 1;
-    while (lanes < 32 && lanes * 4 <= r.splits) lanes *= 2;
-    r.lanes = lanes;
-    hipLaunchKernelGGL(sf_wgrad_reduce_kernel, dim3(cdiv(total, SF_THREADS / lanes)), dim3(SF_THREADS), 0, s, r);
+    launch_wgrad_reduce(d, (const float*)workspace, wgs, w.cop, w.cip, false, dw, out_scale, zero_first, s);
     return check_launch("conv_c_bwd_reduce");
 }
 
@@ -1372,13 +1395,7 @@ static int bgemm_impl(int64_t M, int32_t N, int32_t K, const void* A, int32_t ld
     REQUIRE(!(bias || resid) || N % 8 == 0, "sf_bgemm: bias / residual need N %% 8 == 0");
     REQUIRE(nbatch >= 1 && bh >= 1 && nbatch % bh == 0 && nbatch <= 65535, "sf_bgemm: bad batch (%d, %d)", nbatch, bh);
     REQUIRE(!resid || (ldr % 8 == 0 && ldr >= N), "sf_bgemm: bad residual pitch");
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.g = gather_matrix(A, M, K, lda);
-    p.M = (int)M;
-    p.wmat = (const f16*)W; p.ldw = ldw; p.Nout = N;
-    p.ksteps = cdiv(K, 32);
-    p.y = (f16*)Y; p.ldy = ldy; p.bias = bias; p.resid = (const f16*)resid; p.ldr = ldr;
+    IgemmParams p = gemm_params(gather_matrix(A, M, K, lda), (int)M, W, ldw, N, Y, ldy, bias, resid, ldr);
     p.bh = bh; p.sa_b = sa_b; p.sa_h = sa_h; p.sw_b = sw_b; p.sw_h = sw_h; p.sy_b = sy_b; p.sy_h = sy_h;
     p.linear = 1;
     p.sr_b = sr_b; p.sr_h = sr_h; p.resid_row0 = resid_row0; p.alpha = alpha;
@@ -1386,13 +1403,9 @@ static int bgemm_impl(int64_t M, int32_t N, int32_t K, const void* A, int32_t ld
         REQUIRE(nbatch == 1 && N % 8 == 0, "sf_gemm_rows32: one GEMM, N %% 8 == 0 (N=%d)", N);
         if (rows32_arg("sf_gemm_rows32", side, M, N, true, p.f32)) return -1;
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (try_igemm2(p, s, nbatch)) return check_launch("bgemm2");
-    if (N > 64) { p.ntiles_n = cdiv(N, 128); launch_igemm<128, 64, 64>(p, true, s, nbatch); }
-    else if (N > 32) { p.ntiles_n = 1; launch_igemm<64, 32, 64>(p, true, s, nbatch); }
-    else if (N > 16) { p.ntiles_n = 1; launch_igemm<32, 32, 32>(p, true, s, nbatch); }
-    else { p.ntiles_n = 1; launch_igemm<16, 32, 16>(p, true, s, nbatch); }
-    return check_launch("bgemm");
+    const GemmPlan g = plan_gemm(p, true, nbatch);
+    launch_gemm(g, p, (hipStream_t)stream);
+    return check_launch(g.kind == GEMM_GEN2 ? "bgemm2" : "bgemm");
 }
 
 extern "C" int sf_bgemm(int64_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* W, int32_t ldw,
@@ -1418,26 +1431,15 @@ static int gemm_act_impl(int64_t M, int32_t N, int32_t K, const void* A, int32_t
     REQUIRE(N % 8 == 0 && K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && ldy % 8 == 0 && ldaux % 8 == 0 && ldaux >= N,
             "sf_gemm_act: N, K and the pitches must be multiples of 8");
     REQUIRE(mode == 1 || mode == 2, "sf_gemm_act: mode must be 1 (write gelu(y)) or 2 (multiply by gelu'(aux))");
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.g = gather_matrix(A, M, K, lda);
-    p.M = (int)M;
-    p.wmat = (const f16*)W; p.ldw = ldw; p.Nout = N;
-    p.ksteps = cdiv(K, 32);
-    p.y = (f16*)Y; p.ldy = ldy; p.bias = bias;
+    IgemmParams p = gemm_params(gather_matrix(A, M, K, lda), (int)M, W, ldw, N, Y, ldy, bias, nullptr, 0);
     p.bh = 1;
     p.act_mode = mode; p.act_aux = (f16*)aux; p.ld_aux = ldaux;
     p.linear = 1;
     p.bnb_part = colsum_part;          // bnb_y == nullptr: plain column sums of the stored tile, one row per M tile
-    hipStream_t s = (hipStream_t)stream;
-    if (colsum_rows) *colsum_rows = colsum_part ? cdiv(p.M, 256) : 0;
-    if (try_igemm2(p, s, 1)) return check_launch("gemm_act2");
-    if (colsum_rows) *colsum_rows = colsum_part ? cdiv(p.M, 128) : 0;
-    if (N > 64) { p.ntiles_n = cdiv(N, 128); launch_igemm<128, 64, 64>(p, true, s, 1); }
-    else if (N > 32) { p.ntiles_n = 1; launch_igemm<64, 32, 64>(p, true, s, 1); }
-    else if (N > 16) { p.ntiles_n = 1; launch_igemm<32, 32, 32>(p, true, s, 1); }
-    else { p.ntiles_n = 1; launch_igemm<16, 32, 16>(p, true, s, 1); }
-    return check_launch("gemm_act");
+    const GemmPlan g = plan_gemm(p, true, 1);
+    if (colsum_rows) *colsum_rows = colsum_part ? cdiv(p.M, g.bm) : 0;
+    launch_gemm(g, p, (hipStream_t)stream);
+    return check_launch(g.kind == GEMM_GEN2 ? "gemm_act2" : "gemm_act");
 }
 
 extern "C" int sf_gemm_act(int64_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* W, int32_t ldw,
@@ -1469,12 +1471,9 @@ extern "C" int sf_bgemm_tn(int64_t M, int32_t R, int32_t Kc, const void* P, int3
     p.nchunks = cdiv(M, 32);
     p.bh = bh; p.sp_b = sp_b; p.sp_h = sp_h; p.sx_b = sx_b; p.sx_h = sx_h; p.so_b = so_b; p.so_h = so_h;
     p.out16 = (f16*)Out; p.ldo = ldo; p.out_scale = scale;
-    hipStream_t s = (hipStream_t)stream;
-    const int tiles_k = cdiv(Kc, 128);
-    if (R >= 128) { p.chunks_per_split = p.nchunks; launch_wgrad<128, 64, 64, 1>(p, dim3(tiles_k, cdiv(R, 128), nbatch), s); }
-    else if (R >= 64) { p.chunks_per_split = p.nchunks; launch_wgrad<64, 32, 64, 1>(p, dim3(tiles_k, cdiv(R, 64), nbatch), s); }
-    else if (R >= 32) { p.chunks_per_split = roundup(p.nchunks, 4); launch_wgrad<32, 32, 32, 4>(p, dim3(tiles_k, cdiv(R, 32), nbatch), s); }
-    else { p.chunks_per_split = roundup(p.nchunks, 4); launch_wgrad<16, 16, 32, 4>(p, dim3(tiles_k, cdiv(R, 16), nbatch), s); }
+    const int bmw = wgrad1_bmw(R);
+    p.chunks_per_split = roundup(p.nchunks, wgrad1_ks(bmw));        // one split of whole stages
+    launch_wgrad1(bmw, p, dim3(cdiv(Kc, 128), cdiv(R, bmw), nbatch), (hipStream_t)stream);
     return check_launch("bgemm_tn");
 }
 
@@ -1865,8 +1864,7 @@ static bool dwrot_plan(const sf_dw_desc* d, int dir, DwSweepParams& p, int& kmod
 }
 static void dwrot_launch(DwSweepParams& p, int kmode, int ks, int sl, bool stats, hipStream_t s) {
     const dim3 grid((unsigned)(p.N * p.tiles_h * p.tiles_w * p.nchunks));
-    static const bool trace = test_hook("SF_TRACE", 0) != 0;
-    if (trace) fprintf(stderr, "[sfamd] dwrot: mode %d s=%d SL=%d N=%d C=%d T=%d a %dx%d it %dx%d TH=%d TW=%d tiles %dx%d RA=%d CA=%d RP=%d slot %d "
+    if (sf_trace()) fprintf(stderr, "[sfamd] dwrot: mode %d s=%d SL=%d N=%d C=%d T=%d a %dx%d it %dx%d TH=%d TW=%d tiles %dx%d RA=%d CA=%d RP=%d slot %d "
                        "(b %d) ring %d grp=%d seg=%d blocks=%u\n", kmode, ks, sl, p.N, p.C, p.T, p.Ha, p.Wa, p.Hit, p.Wit, p.TH, p.TW, p.tiles_h, p.tiles_w,
                        p.RA, p.CA, p.RP, p.slotb, p.slotbB, p.nr, p.ngrp, p.nseg, grid.x);
 #define SF_DWR_LAUNCH(M, S, L, ST) hipLaunchKernelGGL((sf_dwrot_kernel<M, S, L, ST>), grid, dim3(SF_THREADS), 0, s, p)
@@ -1883,8 +1881,7 @@ static void dwrot_launch(DwSweepParams& p, int kmode, int ks, int sl, bool stats
 }
 static void dwsweep_launch(DwSweepParams& p, bool stats, hipStream_t s) {
     const dim3 grid((unsigned)(p.N * p.tiles_h * p.tiles_w * p.nchunks));
-    static const bool trace = test_hook("SF_TRACE", 0) != 0;
-    if (trace) fprintf(stderr, "[sfamd] dwsweep: mode 1 s=2 N=%d C=%d T=%d a %dx%d it %dx%d TH=%d TW=%d tiles %dx%d RA=%d CA=%d RP=%d slot %d "
+    if (sf_trace()) fprintf(stderr, "[sfamd] dwsweep: mode 1 s=2 N=%d C=%d T=%d a %dx%d it %dx%d TH=%d TW=%d tiles %dx%d RA=%d CA=%d RP=%d slot %d "
                        "(b %d) grp=%d seg=%d SL=%d blocks=%u\n", p.N, p.C, p.T, p.Ha, p.Wa, p.Hit, p.Wit, p.TH, p.TW, p.tiles_h, p.tiles_w,
                        p.RA, p.CA, p.RP, p.slotb, p.slotbB, p.ngrp, p.nseg, p.SL, grid.x);
     if (stats) hipLaunchKernelGGL((sf_dwsweep_kernel<1, 2, true>), grid, dim3(SF_THREADS), 0, s, p);
@@ -1931,8 +1928,7 @@ static bool dwtemp_plan(const sf_dw_desc* d, int dir, DwTempParams& p) {
 static int dwtemp_blocks(const DwTempParams& p) { return (int)cdiv(cdiv((int64_t)p.cols, (int64_t)p.PP), (int64_t)p.iters); }
 static void dwtemp_launch(DwTempParams& p, int kT, int dir, bool stats, hipStream_t s) {
     const dim3 grid((unsigned)dwtemp_blocks(p));
-    static const bool trace = test_hook("SF_TRACE", 0) != 0;
-    if (trace) fprintf(stderr, "[sfamd] dwtemporal: dir %d kT=%d N=%d C=%d T=%d HW=%d PP=%d iters=%d blocks=%u\n", dir, kT, p.N, p.C, p.T, p.HW, p.PP, p.iters, grid.x);
+    if (sf_trace()) fprintf(stderr, "[sfamd] dwtemporal: dir %d kT=%d N=%d C=%d T=%d HW=%d PP=%d iters=%d blocks=%u\n", dir, kT, p.N, p.C, p.T, p.HW, p.PP, p.iters, grid.x);
 #define SF_DWTP_LAUNCH(K) do {                                                                                                   \
         if (dir == 2) hipLaunchKernelGGL((sf_dwtemporal_kernel<K, 2, false>), grid, dim3(SF_THREADS), 0, s, p);                    \
         else if (stats) hipLaunchKernelGGL((sf_dwtemporal_kernel<K, 0, true>), grid, dim3(SF_THREADS), 0, s, p);                   \
