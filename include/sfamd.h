@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 32
+#define SF_ABI_VERSION 33
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -539,6 +539,32 @@ int sf_randaug_hist_u8(const void* src, int32_t N, int32_t T, int32_t Hs, int32_
                        const int32_t* table_dev, int32_t* hist, sf_stream_t stream);
 int sf_randaug_layer_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
                         const int32_t* table_dev, const int32_t* hist, void* lut, sf_stream_t stream);
+/* SSL colour augmentation of the batch on the device (ABI 33) -- replaces transform.color_jitter_video_ssl
+ * (slowfast/datasets/transform.py:1073-1121, GaussianBlur at :1145-1157; applied at datasets/kinetics.py:378-387): torchvision's
+ * ColorJitter (brightness, contrast, saturation, hue in a drawn order), RandomGrayscale and PIL's Gaussian blur on ONE image per
+ * clip, the (T * h) x w stack of its frames.  src / dst are dense uint8 [N][T][Hs][Ws][3] buffers as above.  The draw is the
+ * caller's: ONE table of N rows of 16 int32 words, given twice (table_host is validated and decides what is launched; table_dev,
+ * the same words in device memory, is what the kernels read).  A row holds the flags (1 jitter, 2 grey, 4 blur, 8 grey before
+ * the jitter), the op order (four 4-bit fields: 0 brightness, 1 contrast, 2 saturation, 3 hue, 7 nothing), the three blend
+ * factors (float bits), the hue shift 0 .. 255, the box blur's integer radius (0 or 1) and its two 8.24 fixed-point weights,
+ * h, w, and five zeros (csrc/sf_sslcolor.h).  Inside a sample's h x w region the bytes are PIL's, bit for bit; outside it the
+ * streaming pass copies src and the blur passes write nothing.  Kernel launches only; the only atomics are integer adds.
+ *
+ * sf_sslcolor_hist_u8: hist[n * 256 + v] = how many valid pixels of clip n have L = v after the ops drawn before contrast, for the
+ *   clips that drew contrast; the others are left untouched, and with no such row nothing is launched.
+ * sf_sslcolor_stream_u8: the jitter and grey of every row, src -> dst; dst may be src itself (in place: rows without jitter and
+ *   grey are skipped, and nothing is launched when there is no other row) or a buffer that does not overlap it (rows without
+ *   them are copied).  hist may be NULL when no row drew contrast.
+ * sf_sslcolor_blur_rows_u8 / _cols_u8: the three box iterations along the rows / the stacked columns of the clips with the blur
+ *   flag, src -> dst (another buffer), valid region only; no such row: nothing is launched.  Ws <= 4096. */
+int sf_sslcolor_hist_u8(const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
+                        const int32_t* table_dev, int32_t* hist, sf_stream_t stream);
+int sf_sslcolor_stream_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
+                          const int32_t* table_dev, const int32_t* hist, sf_stream_t stream);
+int sf_sslcolor_blur_rows_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
+                             const int32_t* table_dev, sf_stream_t stream);
+int sf_sslcolor_blur_cols_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
+                             const int32_t* table_dev, sf_stream_t stream);
 /* Stochastic depth -- replaces drop_path() (slowfast/models/common.py:46-59) at the two residual additions of
  * MultiScaleBlock (attention.py:500-510): y[m] = (resid ? resid[m] : 0) + scale[m / rows_per_sample] * x[m], with
  * scale[b] = floor(keep_prob + u_b) / keep_prob sampled by the caller.  Rows are fp16 [M][C], C % 8 == 0. */

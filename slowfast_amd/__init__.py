@@ -23,4 +23,6 @@ from .color_augmentation import (ColorAugmentation, ColorRow, ColorTable, constr
                                  color_clip)  # (colour jitter / PCA lighting / normalisation of the AVA clip on the device)
 from .rand_augment import (RandAugment, AugRow, AugTable, construct_rand_augment,  # noqa: F401,E402
                            rand_augment_clip)  # (RandAugment of the decoded uint8 frames on the device)
+from .ssl_color import (SslColorJitter, SslRow, SslTable, construct_ssl_color_jitter,  # noqa: F401,E402
+                        ssl_color_clip)  # (SSL colour jitter / grey / blur of the decoded uint8 frames on the device)
 from .losses import get_loss_func  # noqa: F401,E402

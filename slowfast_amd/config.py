@@ -100,7 +100,12 @@ _DEFAULTS = {
              "TRAIN_JITTER_MOTION_SHIFT": False, "INV_UNIFORM_SAMPLE": False, "RANDOM_FLIP": True,
              # slowfast/config/defaults.py:672-679 (PCA lighting jitter, color_augmentation.construct_color_augmentation)
              "TRAIN_PCA_EIGVAL": [0.225, 0.224, 0.229],
-             "TRAIN_PCA_EIGVEC": [[-0.5675, 0.7192, 0.4009], [-0.5808, -0.0045, -0.8140], [-0.5836, -0.6948, 0.4203]]},
+             "TRAIN_PCA_EIGVEC": [[-0.5675, 0.7192, 0.4009], [-0.5808, -0.0045, -0.8140], [-0.5836, -0.6948, 0.4203]],
+             # slowfast/config/defaults.py:754-791 (ssl_color.construct_ssl_color_jitter; the reference hands the two blur
+             # ranges to color_jitter_video_ssl, which never reads them: neither does this package)
+             "COLOR_RND_GRAYSCALE": 0.0, "SSL_COLOR_JITTER": False, "SSL_COLOR_BRI_CON_SAT": [0.4, 0.4, 0.4],
+             "SSL_COLOR_HUE": 0.1, "SSL_MOCOV2_AUG": False, "SSL_BLUR_SIGMA_MIN": [0.0, 0.1],
+             "SSL_BLUR_SIGMA_MAX": [0.0, 2.0]},
     "SOLVER": {"BASE_LR": 0.1, "MOMENTUM": 0.9, "DAMPENING": 0.0, "NESTEROV": True, "WEIGHT_DECAY": 1e-4,
                "OPTIMIZING_METHOD": "sgd", "ZERO_WD_1D_PARAM": False, "CLIP_GRAD_VAL": None,
                "CLIP_GRAD_L2NORM": None, "LAYER_DECAY": 1.0},

@@ -22,6 +22,7 @@
 #include "sf_sample.h"
 #include "sf_color.h"
 #include "sf_randaug.h"
+#include "sf_sslcolor.h"
 #include "sf_hog.h"
 #include "sf_pixel.h"
 
@@ -3027,6 +3028,125 @@ extern "C" int sf_randaug_layer_u8(const void* src, void* dst, int32_t N, int32_
     hipLaunchKernelGGL(sf_randaug_stream_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
                        (hipStream_t)stream, p);
     return check_launch("randaug_stream");
+}
+
+// ================================================================================================
+// SSL colour augmentation of the batch (sf_sslcolor.h; replaces transform.color_jitter_video_ssl on the decoded frames,
+// datasets/kinetics.py:378-387).  One table with a row per clip (layout: sf_sslcolor.h); the HOST copy is validated and decides
+// what is launched, the kernels read the device copy.  Kernel launches only.
+// counts the rows that need the histogram / the streaming pass / the blur; -1 for a bad table
+static int check_sslcolor_table(const char* who, const int32_t* th, int32_t N, int32_t Hs, int32_t Ws, int& hist_rows,
+                                int& stream_rows, int& blur_rows) {
+    REQUIRE(th, "%s: null table", who);
+    hist_rows = stream_rows = blur_rows = 0;
+    for (int n = 0; n < N; ++n) {
+        const int32_t* w = th + (int64_t)n * SF_SSLCOLOR_ROW_WORDS;
+        const int flags = w[0], order = w[1];
+        REQUIRE(flags >= 0 && flags < 16, "%s: row %d: unknown flags %d", who, n, flags);
+        REQUIRE(w[9] > 0 && w[9] <= Hs && w[10] > 0 && w[10] <= Ws, "%s: row %d: valid size %d x %d is not inside the %d x %d buffer",
+                who, n, w[9], w[10], Hs, Ws);
+        if (flags & SF_SSLCOLOR_JITTER) {
+            REQUIRE(order >= 0 && order < (1 << 16), "%s: row %d: the op order has more than four fields", who, n);
+            int seen = 0;
+            for (int k = 0; k < 4; ++k) {
+                const int op = (order >> (4 * k)) & 15;
+                if (op == SF_SSLCOLOR_NOP) continue;
+                REQUIRE(op < 4, "%s: row %d: unknown op code %d", who, n, op);
+                REQUIRE(!(seen & (1 << op)), "%s: row %d: op %d is drawn twice", who, n, op);
+                seen |= 1 << op;
+            }
+            for (int k = 2; k <= 4; ++k)
+                REQUIRE((w[k] & 0x7f800000) != 0x7f800000, "%s: row %d: blend factor %d is not a finite float", who, n, k - 2);
+            REQUIRE(w[5] >= 0 && w[5] <= 255, "%s: row %d: the hue shift is 0 .. 255 (got %d)", who, n, w[5]);
+        }
+        if (flags & SF_SSLCOLOR_BLUR) {
+            REQUIRE(w[6] >= 0 && 3 * (w[6] + 1) <= SF_SSLCOLOR_HALO, "%s: row %d: box radius %d is not 0 or 1 (sigma <= 2)", who, n, w[6]);
+            REQUIRE(w[7] > 0 && w[8] >= 0 && (int64_t)(2 * w[6] + 1) * w[7] + 2 * (int64_t)w[8] <= (1 << 24),
+                    "%s: row %d: the box weights do not sum to 2^24 or less", who, n);
+        }
+        hist_rows += sslcolor_needs_hist(flags, order);
+        stream_rows += (flags & (SF_SSLCOLOR_JITTER | SF_SSLCOLOR_GREY)) != 0;
+        blur_rows += (flags & SF_SSLCOLOR_BLUR) != 0;
+    }
+    return 0;
+}
+static int fill_sslcolor_params(const char* who, SslColorParams& p, const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
+                                const int32_t* table_dev) {
+    REQUIRE(src && table_dev, "%s: null pointer", who);
+    REQUIRE(N > 0 && T > 0 && (int64_t)N * T <= 65535, "%s: bad shape (N * T must be 1 .. 65535)", who);
+    REQUIRE(Hs > 0 && Ws > 0 && Hs < (1 << 16) && Ws < (1 << 16) && (int64_t)Hs * Ws * 3 < (1ll << 31),
+            "%s: a frame of %d x %d is empty or has 2^31 bytes or more", who, Hs, Ws);
+    memset(&p, 0, sizeof(p));
+    p.src = (const unsigned char*)src; p.table = table_dev; p.N = N; p.T = T; p.Hs = Hs; p.Ws = Ws; p.slab = Hs * Ws;
+    p.fdW = make_fastdiv((uint32_t)Ws);
+    return 0;
+}
+extern "C" int sf_sslcolor_hist_u8(const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
+                                   const int32_t* table_dev, int32_t* hist, sf_stream_t stream) {
+    SslColorParams p;
+    if (fill_sslcolor_params("sf_sslcolor_hist_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
+    int hist_rows, stream_rows, blur_rows;
+    if (check_sslcolor_table("sf_sslcolor_hist_u8", table_host, N, Hs, Ws, hist_rows, stream_rows, blur_rows)) return -1;
+    if (hist_rows == 0) return 0;                           // nothing to count: nothing is launched
+    REQUIRE(hist && (uintptr_t)hist % 4 == 0, "sf_sslcolor_hist_u8: hist must be a 4-byte aligned pointer");
+    p.hist = hist;
+    p.vec = (uintptr_t)src % 16 == 0 && p.slab % SF_RANDAUG_PIX == 0;
+    hipLaunchKernelGGL(sf_sslcolor_hist_zero_kernel, dim3(N), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    if (check_launch("sslcolor_hist_zero")) return -1;
+    hipLaunchKernelGGL(sf_sslcolor_hist_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
+                       (hipStream_t)stream, p);
+    return check_launch("sslcolor_hist");
+}
+extern "C" int sf_sslcolor_stream_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
+                                     const int32_t* table_host, const int32_t* table_dev, const int32_t* hist, sf_stream_t stream) {
+    SslColorParams p;
+    if (fill_sslcolor_params("sf_sslcolor_stream_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
+    const int64_t bytes = (int64_t)N * T * p.slab * 3;
+    REQUIRE(dst, "sf_sslcolor_stream_u8: null dst");
+    REQUIRE(dst == src || (const unsigned char*)dst + bytes <= (const unsigned char*)src || (const unsigned char*)src + bytes <= (const unsigned char*)dst,
+            "sf_sslcolor_stream_u8: dst must be src itself (in place) or must not overlap it");
+    int hist_rows, stream_rows, blur_rows;
+    if (check_sslcolor_table("sf_sslcolor_stream_u8", table_host, N, Hs, Ws, hist_rows, stream_rows, blur_rows)) return -1;
+    REQUIRE(hist_rows == 0 || hist, "sf_sslcolor_stream_u8: a row with contrast needs the histograms");
+    if (stream_rows == 0 && dst == src) return 0;           // in place and nothing drawn: nothing is launched
+    p.dst = (unsigned char*)dst; p.hist = const_cast<int32_t*>(hist);
+    p.vec = (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 && p.slab % SF_RANDAUG_PIX == 0;
+    hipLaunchKernelGGL(sf_sslcolor_stream_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
+                       (hipStream_t)stream, p);
+    return check_launch("sslcolor_stream");
+}
+static int sslcolor_blur(const char* who, bool cols, const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
+                         const int32_t* table_host, const int32_t* table_dev, sf_stream_t stream) {
+    SslColorParams p;
+    if (fill_sslcolor_params(who, p, src, N, T, Hs, Ws, table_dev)) return -1;
+    const int64_t bytes = (int64_t)N * T * p.slab * 3;
+    REQUIRE(dst && ((const unsigned char*)dst + bytes <= (const unsigned char*)src || (const unsigned char*)src + bytes <= (const unsigned char*)dst),
+            "%s: dst must be another buffer than src", who);
+    REQUIRE(Ws <= SF_SSLCOLOR_MAX_W, "%s: frames wider than %d pixels are not supported", who, SF_SSLCOLOR_MAX_W);
+    REQUIRE(N <= 65535 && (int64_t)T * Hs < (1 << 24), "%s: bad shape (N <= 65535, T * Hs < 2^24)", who);
+    int hist_rows, stream_rows, blur_rows;
+    if (check_sslcolor_table(who, table_host, N, Hs, Ws, hist_rows, stream_rows, blur_rows)) return -1;
+    if (blur_rows == 0) return 0;                           // nothing is launched
+    p.dst = (unsigned char*)dst;
+    const int stack = T * Hs;
+    if (cols) {
+        p.vec = Ws % 4 == 0 && (uintptr_t)src % 4 == 0 && (uintptr_t)dst % 4 == 0;
+        hipLaunchKernelGGL(sf_sslcolor_blur_cols_kernel, dim3(cdiv(Ws, SF_SSLCOLOR_COLS), cdiv(stack, SF_SSLCOLOR_RUN), N),
+                           dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+        return check_launch("sslcolor_blur_cols");
+    }
+    p.rows = SF_SSLCOLOR_ROW_LDS / (3 * Ws);                // >= 1: Ws <= SF_SSLCOLOR_MAX_W
+    if (p.rows > 8) p.rows = 8;
+    hipLaunchKernelGGL(sf_sslcolor_blur_rows_kernel, dim3(cdiv(stack, p.rows), N), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("sslcolor_blur_rows");
+}
+extern "C" int sf_sslcolor_blur_rows_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
+                                        const int32_t* table_host, const int32_t* table_dev, sf_stream_t stream) {
+    return sslcolor_blur("sf_sslcolor_blur_rows_u8", false, src, dst, N, T, Hs, Ws, table_host, table_dev, stream);
+}
+extern "C" int sf_sslcolor_blur_cols_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
+                                        const int32_t* table_host, const int32_t* table_dev, sf_stream_t stream) {
+    return sslcolor_blur("sf_sslcolor_blur_cols_u8", true, src, dst, N, T, Hs, Ws, table_host, table_dev, stream);
 }
 
 static int row_scale_add_impl(const void* x, int32_t ldx, const float* scale, int64_t rows_per_sample, const void* resid,

@@ -11,7 +11,7 @@ import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 32
+ABI_VERSION = 33
 # 16-bit storage type of activations / packed weights / MFMA operands, fixed per PROCESS: SF_ACT_DTYPE=fp16 (default) loads
 # libsfamd.so, =bf16 loads libsfamd_bf16.so -- the same sources compiled with -DSF_ACT_BF16 (bfloat16 storage,
 # v_mfma_f32_16x16x32_bf16); both are what torch.cuda.amp.autocast admits on the reference side (tools/train_net.py:101-118).
@@ -197,6 +197,10 @@ _SIGNATURES = {
     "sf_randaug_chunk": (c_int, []),
     "sf_randaug_hist_u8": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "sf_randaug_layer_u8": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "sf_sslcolor_hist_u8": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "sf_sslcolor_stream_u8": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "sf_sslcolor_blur_rows_u8": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "sf_sslcolor_blur_cols_u8": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "sf_hog_targets_f32": (c_int, [_F, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _F, _P]),
     "sf_mask_tokens_fwd": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32,
                                    c_int32, _F, _F, _P]),
