@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 33
+#define SF_ABI_VERSION 34
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -724,6 +724,32 @@ int sf_token_restore_bwd(const void* dy, int32_t lddy, void* de, int32_t ldde, i
  * T % ts, u not in {1, ts}, u * p * p * 3 > 8192. */
 int sf_pixel_targets_f32(const float* clip, int32_t B, int32_t T, int32_t H, int32_t W, int32_t ts, int32_t u, int32_t p,
                          int32_t norm, float* out, sf_stream_t stream);
+
+/* MoCo step glue (ABI 34) -- slowfast/models/contrastive.py: Normalize, the "moco" branch of forward, _dequeue_and_enqueue,
+ * _update_history.  Everything is fp32 in every build; no floating-point atomics, every sum has one fixed order.
+ * sf_l2norm_rows: out[r] (dense [n][C]) = x[s] / sqrt(sum_c x[s][c]^2), s = perm ? perm[r] : r, x rows ld floats apart.  No
+ * epsilon: a zero row gives NaN, as the reference's Normalize does.  perm (int32 [n]) is NOT checked here: the caller hands in
+ * a permutation of 0 .. n-1.
+ * sf_moco_nce_slabs, then sf_moco_nce_finalize with the same arguments: f [n][C] raw query features, key [V][n][C]
+ * normalised keys, queue [K][C], inv_T = 1 / T -> logits [V n][1 + K] (row v n + i: column 0 = (q_i . key_v,i) / T, column
+ * 1 + j = (q_i . queue_j) / T, q = f / |f|), loss[0] = mean over the V n rows of (logsumexp - column 0), df [n][C] = d loss / d f.
+ * The queue is read once (by the first call); ws is sf_moco_nce_workspace(n, V, K, C) bytes, 16-byte aligned, and carries the
+ * per-slab softmax partials from the first call to the second.  Rejected: C not a multiple of 64 or > 256, n C > 8192, V > 16,
+ * K < 1.
+ * sf_queue_enqueue: keys [views][rows][C] are written to queue [K][C] block after block at ptr[0] (device int64), which wraps to
+ * 0 on reaching K and is stored back.  If ptr[0] < 0 or one of the writes would pass K, NOTHING is written, ptr stays and
+ * err[0] (device int32) is set to 1 -- never an out-of-bounds store.  K % rows != 0 is rejected.
+ * sf_ema_update: hist[i] = fl(fl(p[i] * mm[1]) + fl(hist[i] * mm[0])), mm = device float[2] {m, 1 - m}: three separately
+ * rounded operations, the bits of torch's `p * (1.0 - m) + hist * m`. */
+int sf_l2norm_rows(int32_t n, int32_t C, const float* x, int32_t ld, const int32_t* perm, float* out, sf_stream_t stream);
+int64_t sf_moco_nce_workspace(int32_t n, int32_t V, int32_t K, int32_t C);
+int sf_moco_nce_slabs(int32_t n, int32_t V, int32_t K, int32_t C, const float* f, const float* key, const float* queue,
+                      float inv_T, float* logits, float* df, float* loss, void* ws, int64_t ws_bytes, sf_stream_t stream);
+int sf_moco_nce_finalize(int32_t n, int32_t V, int32_t K, int32_t C, const float* f, const float* key, const float* queue,
+                         float inv_T, float* logits, float* df, float* loss, void* ws, int64_t ws_bytes, sf_stream_t stream);
+int sf_queue_enqueue(int32_t K, int32_t C, int32_t rows, int32_t views, const float* keys, float* queue, int64_t* ptr,
+                     int32_t* err, sf_stream_t stream);
+int sf_ema_update(int64_t n, const float* p, float* hist, const float* mm, sf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -105,7 +105,9 @@ _DEFAULTS = {
              # ranges to color_jitter_video_ssl, which never reads them: neither does this package)
              "COLOR_RND_GRAYSCALE": 0.0, "SSL_COLOR_JITTER": False, "SSL_COLOR_BRI_CON_SAT": [0.4, 0.4, 0.4],
              "SSL_COLOR_HUE": 0.1, "SSL_MOCOV2_AUG": False, "SSL_BLUR_SIGMA_MIN": [0.0, 0.1],
-             "SSL_BLUR_SIGMA_MAX": [0.0, 2.0]},
+             "SSL_BLUR_SIGMA_MAX": [0.0, 2.0],
+             # slowfast/config/defaults.py:749-752 (crops per video: the views of the contrastive models)
+             "TRAIN_CROP_NUM_TEMPORAL": 1, "TRAIN_CROP_NUM_SPATIAL": 1},
     "SOLVER": {"BASE_LR": 0.1, "MOMENTUM": 0.9, "DAMPENING": 0.0, "NESTEROV": True, "WEIGHT_DECAY": 1e-4,
                "OPTIMIZING_METHOD": "sgd", "ZERO_WD_1D_PARAM": False, "CLIP_GRAD_VAL": None,
                "CLIP_GRAD_L2NORM": None, "LAYER_DECAY": 1.0},
@@ -114,8 +116,12 @@ _DEFAULTS = {
     # the arithmetic is the pytorch backend's)
     "AVA": {"BGR": False, "TRAIN_USE_COLOR_AUGMENTATION": False, "TRAIN_PCA_JITTER_ONLY": True, "TEST_FORCE_FLIP": False},
     "MULTIGRID": {"SHORT_CYCLE": False, "LONG_CYCLE": False},
-    "CONTRASTIVE": {"NUM_MLP_LAYERS": 1, "MLP_DIM": 2048, "BN_MLP": False, "BN_SYNC_MLP": False,
-                    "PREDICTOR_DEPTHS": []},
+    # slowfast/config/defaults.py:21-90 (contrastive.ContrastiveModel; TYPE "moco" is the one that runs here)
+    "CONTRASTIVE": {"T": 0.07, "DIM": 128, "LENGTH": 239975, "QUEUE_LEN": 65536, "MOMENTUM": 0.5, "MOMENTUM_ANNEALING": False,
+                    "TYPE": "mem", "INTERP_MEMORY": False, "MEM_TYPE": "1d", "NUM_CLASSES_DOWNSTREAM": 400,
+                    "NUM_MLP_LAYERS": 1, "MLP_DIM": 2048, "BN_MLP": False, "BN_SYNC_MLP": False, "LOCAL_SHUFFLE_BN": True,
+                    "MOCO_MULTI_VIEW_QUEUE": False, "DELTA_CLIPS_MIN": float("-inf"), "DELTA_CLIPS_MAX": float("inf"),
+                    "PREDICTOR_DEPTHS": [], "SEQUENTIAL": False, "SIMCLR_DIST_ON": True, "SWAV_QEUE_LEN": 0, "KNN_ON": True},
     # slowfast/config/defaults.py:447-558
     "MVIT": {"MODE": "conv", "POOL_FIRST": False, "CLS_EMBED_ON": True, "PATCH_KERNEL": [3, 7, 7],
              "PATCH_STRIDE": [2, 4, 4], "PATCH_PADDING": [2, 4, 4], "PATCH_2D": False, "EMBED_DIM": 96, "NUM_HEADS": 1,
@@ -148,6 +154,7 @@ _DEFAULTS = {
     "VIS_MASK": {"ENABLE": False},
     "NUM_GPUS": 1, "NUM_SHARDS": 1, "SHARD_ID": 0, "RNG_SEED": 1, "LOG_MODEL_INFO": True, "DIST_BACKEND": "nccl",
     "OUTPUT_DIR": ".",
+    "TASK": "",         # slowfast/config/defaults.py:887 ("ssl" in the self-supervised recipes)
 }
 
 
@@ -317,6 +324,22 @@ PRESETS["SLOW_8x8_R50"] = _variant("C2D_8x8_R50", ARCH="slow")      # configs/Ki
 PRESETS["SLOW_8x8_R50"]["NONLOCAL"]["INSTANTIATION"] = "dot_product"
 PRESETS["I3D_8x8_R50"] = _variant("C2D_8x8_R50", ARCH="i3d")        # configs/Kinetics/I3D_8x8_R50.yaml
 
+
+# configs/contrastive_ssl/MoCo_SlowR50_8x8.yaml (MoCo pre-training of Slow-R50: 4 temporal crops, each the query once against
+# the momentum encoder's keys of the others; NUM_GPUS stays 1 here: the cross-rank shuffle is not built)
+PRESETS["MoCo_SlowR50_8x8"] = copy.deepcopy(PRESETS["SLOW_8x8_R50"])
+PRESETS["MoCo_SlowR50_8x8"]["TASK"] = "ssl"
+PRESETS["MoCo_SlowR50_8x8"]["TRAIN"] = {"BATCH_SIZE": 64, "MIXED_PRECISION": True}
+PRESETS["MoCo_SlowR50_8x8"]["RESNET"]["ZERO_INIT_FINAL_BN"] = False     # the yaml leaves the default
+PRESETS["MoCo_SlowR50_8x8"]["MODEL"] = {"NUM_CLASSES": 128, "ARCH": "slow", "MODEL_NAME": "ContrastiveModel",
+                                         "LOSS_FUNC": "contrastive_loss", "DROPOUT_RATE": 0.0, "HEAD_ACT": "none"}
+PRESETS["MoCo_SlowR50_8x8"]["CONTRASTIVE"] = {"T": 0.1, "NUM_MLP_LAYERS": 3, "SEQUENTIAL": True, "MOCO_MULTI_VIEW_QUEUE": True,
+                                               "MOMENTUM": 0.994, "MOMENTUM_ANNEALING": True, "TYPE": "moco"}
+PRESETS["MoCo_SlowR50_8x8"]["DATA"].update({
+    "TRAIN_CROP_NUM_TEMPORAL": 4, "TRAIN_CROP_NUM_SPATIAL": 1, "TRAIN_JITTER_SCALES_RELATIVE": [0.2, 0.766],
+    "TRAIN_JITTER_ASPECT_RELATIVE": [0.75, 1.3333], "SSL_MOCOV2_AUG": True, "COLOR_RND_GRAYSCALE": 0.2,
+    "SSL_COLOR_JITTER": True, "SSL_COLOR_HUE": 0.15, "SSL_COLOR_BRI_CON_SAT": [0.6, 0.6, 0.6]})
+PRESETS["MoCo_SlowR50_8x8"]["SOLVER"] = {"BASE_LR": 0.1, "MOMENTUM": 0.9, "OPTIMIZING_METHOD": "sgd", "MAX_EPOCH": 200}
 
 # configs/Kinetics/C2D_NLN_8x8_R50.yaml, configs/Kinetics/SLOWFAST_NLN_8x8_R50.yaml
 PRESETS["C2D_NLN_8x8_R50"] = copy.deepcopy(PRESETS["C2D_8x8_R50"])

@@ -25,6 +25,7 @@
 #include "sf_sslcolor.h"
 #include "sf_hog.h"
 #include "sf_pixel.h"
+#include "sf_moco.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -3617,4 +3618,98 @@ extern "C" int sf_pixel_targets_f32(const float* clip, int32_t B, int32_t T, int
     REQUIRE((int64_t)B * 3 * T * H * W < (1ll << 40), "sf_pixel_targets_f32: clip too large");
     hipLaunchKernelGGL(sf_pixel_targets_kernel, dim3(chunks, p.h, (unsigned)gz), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("pixel_targets_f32");
+}
+
+
+// ================================================================================================
+// MoCo step glue (sf_moco.h; slowfast/models/contrastive.py: Normalize, the moco branch of forward, _dequeue_and_enqueue,
+// _update_history).
+extern "C" int sf_l2norm_rows(int32_t n, int32_t C, const float* x, int32_t ld, const int32_t* perm, float* out,
+                              sf_stream_t stream) {
+    REQUIRE(x && out, "sf_l2norm_rows: null pointer");
+    REQUIRE(n > 0 && C > 0 && ld >= C, "sf_l2norm_rows: bad shape (n=%d, C=%d, ld=%d)", n, C, ld);
+    L2NormParams p;
+    p.x = x; p.perm = perm; p.out = out; p.n = n; p.C = C; p.ld = ld;
+    hipLaunchKernelGGL(sf_l2norm_rows_kernel, dim3(cdiv(n, SF_THREADS / 64)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("l2norm_rows");
+}
+
+static int moco_slab_rows(int32_t K) {
+    return SF_MOCO_CHUNK * cdiv(K, (int64_t)SF_MOCO_CHUNK * SF_MOCO_SLABS);
+}
+static int moco_check(const char* who, int32_t n, int32_t V, int32_t K, int32_t C) {
+    REQUIRE(n > 0 && V > 0 && K >= 1, "%s: bad shape (n=%d, V=%d, K=%d)", who, n, V, K);
+    REQUIRE(C > 0 && C % 64 == 0 && C <= 256, "%s: C = %d: the feature dimension must be a multiple of 64 up to 256", who, C);
+    REQUIRE((int64_t)n * C <= SF_MOCO_QMAX, "%s: n * C = %lld is beyond the query rows one workgroup keeps (<= %d)", who,
+            (long long)n * C, SF_MOCO_QMAX);
+    REQUIRE(V <= SF_MOCO_VMAX, "%s: %d key views (<= %d)", who, V, SF_MOCO_VMAX);
+    REQUIRE(((int64_t)V * n) * ((int64_t)K + 1) < (1ll << 40), "%s: logits too large", who);
+    return 0;
+}
+extern "C" int64_t sf_moco_nce_workspace(int32_t n, int32_t V, int32_t K, int32_t C) {
+    if (moco_check("sf_moco_nce_workspace", n, V, K, C)) return -1;
+    const int64_t nslab = cdiv(K, moco_slab_rows(K));
+    return 4 * ((nslab * n * 2 + 3) / 4 * 4 + nslab * n * C);
+}
+static int moco_fill(const char* who, MocoNceParams& p, int32_t n, int32_t V, int32_t K, int32_t C, const float* f,
+                     const float* key, const float* queue, float inv_T, float* logits, float* df, float* loss, void* ws,
+                     int64_t ws_bytes) {
+    if (moco_check(who, n, V, K, C)) return -1;
+    REQUIRE(f && key && queue && logits && df && loss && ws, "%s: null pointer", who);
+    REQUIRE((uintptr_t)queue % 16 == 0 && (uintptr_t)ws % 16 == 0, "%s: the queue and the workspace must be 16-byte aligned", who);
+    REQUIRE(ws_bytes >= sf_moco_nce_workspace(n, V, K, C), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
+            (long long)sf_moco_nce_workspace(n, V, K, C));
+    p.f = f; p.key = key; p.queue = queue; p.logits = logits; p.df = df; p.loss = loss;
+    p.n = n; p.V = V; p.K = K; p.C = C; p.invT = inv_T;
+    p.slab_rows = moco_slab_rows(K);
+    p.nslab = cdiv(K, p.slab_rows);
+    p.ws_ms = (float*)ws;
+    p.ws_a = (float*)ws + ((int64_t)p.nslab * n * 2 + 3) / 4 * 4;
+    return 0;
+}
+extern "C" int sf_moco_nce_slabs(int32_t n, int32_t V, int32_t K, int32_t C, const float* f, const float* key,
+                                 const float* queue, float inv_T, float* logits, float* df, float* loss, void* ws,
+                                 int64_t ws_bytes, sf_stream_t stream) {
+    MocoNceParams p;
+    if (moco_fill("sf_moco_nce_slabs", p, n, V, K, C, f, key, queue, inv_T, logits, df, loss, ws, ws_bytes)) return -1;
+    const dim3 grid(p.nslab), block(SF_THREADS);
+    switch (C) {
+        case 64: hipLaunchKernelGGL(sf_moco_nce_slab_kernel<64>, grid, block, 0, (hipStream_t)stream, p); break;
+        case 128: hipLaunchKernelGGL(sf_moco_nce_slab_kernel<128>, grid, block, 0, (hipStream_t)stream, p); break;
+        case 192: hipLaunchKernelGGL(sf_moco_nce_slab_kernel<192>, grid, block, 0, (hipStream_t)stream, p); break;
+        default: hipLaunchKernelGGL(sf_moco_nce_slab_kernel<256>, grid, block, 0, (hipStream_t)stream, p); break;
+    }
+    return check_launch("moco_nce_slabs");
+}
+extern "C" int sf_moco_nce_finalize(int32_t n, int32_t V, int32_t K, int32_t C, const float* f, const float* key,
+                                    const float* queue, float inv_T, float* logits, float* df, float* loss, void* ws,
+                                    int64_t ws_bytes, sf_stream_t stream) {
+    MocoNceParams p;
+    if (moco_fill("sf_moco_nce_finalize", p, n, V, K, C, f, key, queue, inv_T, logits, df, loss, ws, ws_bytes)) return -1;
+    hipLaunchKernelGGL(sf_moco_nce_finalize_kernel, dim3(n + 1), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("moco_nce_finalize");
+}
+
+extern "C" int sf_queue_enqueue(int32_t K, int32_t C, int32_t rows, int32_t views, const float* keys, float* queue,
+                                int64_t* ptr, int32_t* err, sf_stream_t stream) {
+    REQUIRE(keys && queue && ptr && err, "sf_queue_enqueue: null pointer");
+    REQUIRE(K > 0 && C > 0 && rows > 0 && views > 0, "sf_queue_enqueue: bad shape (K=%d, C=%d, rows=%d, views=%d)", K, C, rows,
+            views);
+    REQUIRE(K % rows == 0, "sf_queue_enqueue: K %% rows != 0 (K=%d, rows=%d): the queue length must be a multiple of the key "
+            "batch", K, rows);
+    EnqueueParams p;
+    p.keys = keys; p.queue = queue; p.ptr = ptr; p.err = err; p.K = K; p.C = C; p.rows = rows; p.views = views;
+    p.vec = C % 4 == 0 && (uintptr_t)keys % 16 == 0 && (uintptr_t)queue % 16 == 0;
+    hipLaunchKernelGGL(sf_queue_enqueue_kernel, dim3(1), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("queue_enqueue");
+}
+
+extern "C" int sf_ema_update(int64_t n, const float* p_, float* hist, const float* mm, sf_stream_t stream) {
+    REQUIRE(p_ && hist && mm && n > 0, "sf_ema_update: bad arguments");
+    REQUIRE((uintptr_t)p_ % 4 == 0 && (uintptr_t)hist % 4 == 0, "sf_ema_update: the buffers must be 4-byte aligned");
+    EmaParams p;
+    p.p = p_; p.hist = hist; p.mm = mm; p.n = n;
+    p.vec = (uintptr_t)p_ % 16 == 0 && (uintptr_t)hist % 16 == 0;
+    hipLaunchKernelGGL(sf_ema_update_kernel, dim3(sf_flat_blocks(n)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("ema_update");
 }

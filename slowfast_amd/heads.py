@@ -42,6 +42,39 @@ class _GlobalMeanFn(torch.autograd.Function):
         return dx
 
 
+class MLPHead(nn.Module):
+    """Projection MLP of the contrastive models (slowfast/models/head_helper.py:147-195): Linear [-> BatchNorm1d] -> ReLU ...
+    -> Linear; with ``bn_on`` only the last Linear has a bias.  Works on (N, C) features: plain torch ops, < 10 MMAC per clip."""
+
+    def __init__(self, dim_in, dim_out, mlp_dim, num_layers, bn_on=False, bias=True, flatten=False, xavier_init=True,
+                 bn_sync_num=1, global_sync=False):
+        super().__init__()
+        if global_sync or bn_sync_num > 1:
+            raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP: the MLP head's BatchNorm is per device")
+        self.flatten = flatten
+        b = False if bn_on else bias
+        mlp_layers = [nn.Linear(dim_in, mlp_dim, bias=b)]
+        mlp_layers[-1].xavier_init = xavier_init
+        for i in range(1, num_layers):
+            if bn_on:
+                mlp_layers.append(nn.BatchNorm1d(num_features=mlp_dim))
+            mlp_layers.append(nn.ReLU(inplace=True))
+            if i == num_layers - 1:
+                d, b = dim_out, bias
+            else:
+                d = mlp_dim
+            mlp_layers.append(nn.Linear(mlp_dim, d, bias=b))
+            mlp_layers[-1].xavier_init = xavier_init
+        self.projection = nn.Sequential(*mlp_layers)
+
+    def forward(self, x):
+        if x.ndim == 5:
+            x = x.permute((0, 2, 3, 4, 1))
+        if self.flatten:
+            x = x.reshape(-1, x.shape[-1])
+        return self.projection(x)
+
+
 class ResNetBasicHead(nn.Module):
     def __init__(self, dim_in, num_classes, pool_size, dropout_rate=0.0, act_func="softmax", detach_final_fc=False,
                  cfg=None):
@@ -56,8 +89,17 @@ class ResNetBasicHead(nn.Module):
         if dropout_rate > 0.0:
             self.dropout = nn.Dropout(dropout_rate)
         mlp_layers = cfg.CONTRASTIVE.NUM_MLP_LAYERS if cfg is not None else 1
-        assert mlp_layers == 1, "MLP projection heads belong to the self-supervised models (out of scope)"
-        self.projection = nn.Linear(sum(dim_in), num_classes, bias=True)
+        if mlp_layers == 1:
+            self.projection = nn.Linear(sum(dim_in), num_classes, bias=True)
+        else:                                   # the projection MLP of the contrastive models (head_helper.py:261-274)
+            if cfg.CONTRASTIVE.BN_SYNC_MLP:
+                raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP: the MLP head's BatchNorm is per device")
+            if list(cfg.CONTRASTIVE.PREDICTOR_DEPTHS):
+                raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS: predictor heads belong to BYOL")
+            self.projection = MLPHead(sum(dim_in), num_classes, cfg.CONTRASTIVE.MLP_DIM, mlp_layers,
+                                      bn_on=cfg.CONTRASTIVE.BN_MLP)
+        # (N, 1, 1, 1, C) -> (N, C) in front of the projection (head_helper.py:324-328): BatchNorm1d needs it
+        self._flatten_pooled = cfg is not None and cfg.MODEL.MODEL_NAME == "ContrastiveModel"
         if act_func == "softmax":
             self.act = nn.Softmax(dim=4)
         elif act_func == "sigmoid":
@@ -87,11 +129,14 @@ class ResNetBasicHead(nn.Module):
             x = self.dropout(x)
         if self.detach_final_fc:
             x = x.detach()
+        if self._flatten_pooled and tuple(x.shape[1:4]) == (1, 1, 1):
+            x = x.view(x.shape[0], -1)
         x = self.projection(x)
         if not self.training:
             if self.act is not None:
                 x = self.act(x)
-            x = x.mean([1, 2, 3])
+            if x.dim() == 5:
+                x = x.mean([1, 2, 3])
         return x.view(x.shape[0], -1)
 
 

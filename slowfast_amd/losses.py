@@ -70,11 +70,26 @@ class MultipleMSELoss(nn.Module):
         return loss_sum, multi_loss
 
 
+class ContrastiveLoss(nn.Module):
+    """InfoNCE on ready-made logits whose column 0 is the positive (losses.py:13-21): cross entropy against class 0.  The MoCo
+    training path does not go through it -- ``contrastive.moco_nce`` produces logits, loss and gradient in one pass over the
+    queue -- it is the loss the table names for ``MODEL.LOSS_FUNC: contrastive_loss`` and what the meters call on logits."""
+
+    def __init__(self, reduction="mean"):
+        super().__init__()
+        self.reduction = reduction
+
+    def forward(self, inputs, dummy_labels=None):
+        targets = torch.zeros(inputs.shape[0], dtype=torch.long, device=inputs.device)
+        return nn.functional.cross_entropy(inputs, targets, reduction=self.reduction)
+
+
 _LOSSES = {
     "cross_entropy": nn.CrossEntropyLoss,
     "bce": nn.BCELoss,
     "bce_logit": nn.BCEWithLogitsLoss,
     "soft_cross_entropy": partial(SoftTargetCrossEntropyLoss, normalize_targets=False),
+    "contrastive_loss": ContrastiveLoss,
     "mse": nn.MSELoss,
     "multi_mse": MultipleMSELoss,
 }

@@ -52,7 +52,10 @@ def init_weights(model, fc_init_std=0.01, zero_init_final_bn=True, zero_init_fin
             if m.bias is not None:
                 nn.init.zeros_(m.bias)
         if isinstance(m, nn.Linear):
-            nn.init.normal_(m.weight, mean=0.0, std=fc_init_std)
+            if getattr(m, "xavier_init", False):        # heads.MLPHead: fvcore's c2_xavier_fill
+                nn.init.kaiming_uniform_(m.weight, a=1)
+            else:
+                nn.init.normal_(m.weight, mean=0.0, std=fc_init_std)
             if m.bias is not None:
                 nn.init.zeros_(m.bias)
 

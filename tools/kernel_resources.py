@@ -8,6 +8,7 @@ import subprocess
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MOCO_KERNELS = "sf_l2norm_rows_kernel,sf_moco_nce_,sf_queue_enqueue_kernel,sf_ema_update_kernel"      # csrc/sf_moco.h
 KEYS = ("VGPRs:", "AGPRs:", "VGPRs Spill:", "SGPRs Spill:", "ScratchSize [bytes/lane]:", "Occupancy [waves/SIMD]:", "LDS Size [bytes/block]:")
 
 
@@ -33,11 +34,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--against", default=None, help="git revision to compare with")
     ap.add_argument("--md", default=None)
-    ap.add_argument("--filter", default=None, help="only kernels whose name contains this substring (e.g. sf_cbwd_kernel)")
+    ap.add_argument("--filter", default=None, help="only kernels whose name contains one of these comma-separated substrings "
+                    "(e.g. sf_cbwd_kernel; `moco` stands for the kernels of csrc/sf_moco.h)")
     a = ap.parse_args()
     new = analyse(ROOT)
     if a.filter:
-        new = {k: v for k, v in new.items() if a.filter in k}
+        subs = [s for s in a.filter.replace("moco", MOCO_KERNELS).split(",") if s]
+        new = {k: v for k, v in new.items() if any(s in k for s in subs)}
     old = None
     if a.against:
         with tempfile.TemporaryDirectory() as tmp:
