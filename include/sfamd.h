@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 34
+#define SF_ABI_VERSION 35
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -750,6 +750,22 @@ int sf_moco_nce_finalize(int32_t n, int32_t V, int32_t K, int32_t C, const float
 int sf_queue_enqueue(int32_t K, int32_t C, int32_t rows, int32_t views, const float* keys, float* queue, int64_t* ptr,
                      int32_t* err, sf_stream_t stream);
 int sf_ema_update(int64_t n, const float* p, float* hist, const float* mm, sf_stream_t stream);
+
+/* BYOL similarity loss (ABI 35) -- slowfast/models/contrastive.py: Normalize on the predictor output, sim_loss (:237-243) and its
+ * loop over the keys in the "byol" branch of forward (:531-535), with the backward.  fp32 in every build, no floating-point
+ * atomics, every sum has one fixed order.
+ * sf_byol_sim_rows, then sf_byol_sim_finalize with the same arguments: p [n] rows of C floats ld floats apart (the RAW predictor
+ * output), key [V][n][C] dense normalised keys, inv_T = 1 / T ->
+ *   loss[0] = sum_v [ -mean_i((q_i . key_v,i) / T) ] / V,  q_i = p_i / |p_i|,
+ *   df [n][C] dense = d loss / d p = -(1 / (V n T)) (S_i - q_i (q_i . S_i)) / |p_i|,  S_i = sum_v key_v,i.
+ * No epsilon: a zero row gives NaN in its df row and in the loss, as the reference's Normalize does.  ws is
+ * sf_byol_sim_workspace(n, V, C) bytes (the per-row terms, from the first call to the second).  Accepted: n >= 1, 1 <= V <= 16,
+ * 1 <= C <= 4096, ld >= C; anything else returns -1 (the workspace query too) before anything is written. */
+int64_t sf_byol_sim_workspace(int32_t n, int32_t V, int32_t C);
+int sf_byol_sim_rows(int32_t n, int32_t V, int32_t C, const float* p, int32_t ld, const float* key, float inv_T, float* df,
+                     float* loss, void* ws, int64_t ws_bytes, sf_stream_t stream);
+int sf_byol_sim_finalize(int32_t n, int32_t V, int32_t C, const float* p, int32_t ld, const float* key, float inv_T, float* df,
+                         float* loss, void* ws, int64_t ws_bytes, sf_stream_t stream);
 
 #ifdef __cplusplus
 }

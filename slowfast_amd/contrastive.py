@@ -1,5 +1,6 @@
-"""MoCo pre-training (slowfast/models/contrastive.py, tools/train_net.py:118-172): ``ContrastiveModel`` with
-``CONTRASTIVE.TYPE == "moco"`` on the engine's backbones, and the step glue the reference runs as torch ops on the device.
+"""MoCo and BYOL pre-training (slowfast/models/contrastive.py, tools/train_net.py:118-172): ``ContrastiveModel`` with
+``CONTRASTIVE.TYPE == "moco"`` or ``"byol"`` on the engine's backbones, on one device, and the step glue the reference runs as
+torch ops on the device.
 
 Per iteration the reference makes three passes per parameter tensor for the momentum update, four small passes per feature matrix
 for ``Normalize``, an ``einsum`` against a clone of the queue, an ``einsum`` / ``unsqueeze`` / ``cat`` per key view, a ``cat``
@@ -16,6 +17,16 @@ host on ``int(self.ptr.item())``.  Here (csrc/sf_moco.h, all fp32, no floating-p
 Nothing reads ``ptr`` or ``iter`` back per iteration: the iteration-0 copy ``hist = p`` is decided from a host mirror of
 ``iter`` (refreshed by ``load_state_dict``), and a pointer that would leave the queue turns the enqueue into a no-op that
 raises an error word the host looks at where it synchronises anyway (``state_dict()``, ``eval()``).
+
+BYOL (``TYPE == "byol"``: predictor heads on the projection, no queue in the loss, no batch shuffle) shares the momentum
+encoder, the annealing and ``l2norm_rows`` for the keys.  Its loss is, per key view, ``Normalize`` of the predictor output, an
+``einsum``, a ``div``, a ``mean`` and a negation, then a sum over views and a division, with the autograd mirror of each.  Here
+(csrc/sf_byol.h, fp32, no floating-point atomics):
+
+* ``byol_sim``     two launches: the loss of one query against all its key views and d(loss)/d(p) for the RAW predictor output.
+  ``ByolSimFn.backward`` is ``grad_out * df``.
+
+The dummy logits the reference builds twice per step (9999 in column 0) are built once per (rows, QUEUE_LEN, device).
 """
 import math
 
@@ -30,7 +41,7 @@ from .registry import MODEL_REGISTRY
 from .video_models import ResNet, SlowFast
 
 _MODEL_TYPES = {"slowfast": SlowFast, "slow": ResNet, "c2d": ResNet, "i3d": ResNet, "slow_c2d": ResNet}
-_UNSUPPORTED_TYPES = ("mem", "self", "byol", "swav", "simclr")
+_UNSUPPORTED_TYPES = ("mem", "self", "swav", "simclr")
 
 
 def _dense_f32(t, what, dim=2):
@@ -117,6 +128,62 @@ def moco_nce(f, keys, queue, T):
     if not torch.is_tensor(keys):
         keys = torch.stack([k for k in keys], 0)
     return MoCoNceFn.apply(f, keys.detach(), queue.detach(), T)
+
+
+_byol_workspaces = {}
+
+
+def _byol_workspace(device, n, V, C):
+    """Per-row loss terms of ``byol_sim``, allocated once per shape."""
+    key = (device, n, V, C)
+    ws = _byol_workspaces.get(key)
+    if ws is None:
+        nbytes = get_lib().call("sf_byol_sim_workspace", n, V, C)
+        ws = _byol_workspaces[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+class ByolSimFn(torch.autograd.Function):
+    """loss = f(raw predictor output p (n, C), normalised keys (V, n, C), T): ``sum_v sim_loss(Normalize(p), key_v) / V`` of the
+    byol branch; differentiable w.r.t. p.  The rows of p may be pitched (``p.stride(0) >= C``)."""
+
+    @staticmethod
+    def forward(ctx, p, keys, T):
+        if not (torch.is_tensor(p) and p.dtype == torch.float32 and p.dim() == 2 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
+            raise SfError("byol_sim: p must be a float32 (n, C) matrix with unit column stride (got %s)" % (
+                "%s %s" % (p.dtype, tuple(p.shape)) if torch.is_tensor(p) else type(p).__name__,))
+        _dense_f32(keys, "byol_sim: keys", 3)
+        stream = ops._stream(p)
+        n, C = p.shape
+        V = keys.shape[0]
+        if tuple(keys.shape[1:]) != (n, C) or keys.device != p.device:
+            raise SfError("byol_sim: keys %s do not match p %s" % (tuple(keys.shape), tuple(p.shape)))
+        lib = get_lib()
+        ws = _byol_workspace(p.device, n, V, C)         # raises for a shape the kernels do not take, before anything is allocated
+        df = torch.empty((n, C), dtype=torch.float32, device=p.device)
+        loss = torch.empty((1,), dtype=torch.float32, device=p.device)
+        args = (n, V, C, p.data_ptr(), p.stride(0), keys.data_ptr(), 1.0 / float(T), df.data_ptr(), loss.data_ptr(),
+                ws.data_ptr(), ws.numel() * 4, stream)
+        lib.call("sf_byol_sim_rows", *args, work=dict(bytes=4.0 * n * C * (V + 2), flops=4.0 * n * C * (V + 1)))
+        lib.call("sf_byol_sim_finalize", *args, work=dict(bytes=4.0 * n))
+        ctx.save_for_backward(df)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (df,) = ctx.saved_tensors
+        return dloss * df, None, None
+
+
+def byol_sim(p, keys, T):
+    """The loss of the byol branch of ``ContrastiveModel.forward`` for one query: ``p`` is the RAW predictor output (the
+    normalisation and its backward are inside), ``keys`` a (V, n, C) tensor or a list of V normalised (n, C) key matrices."""
+    if not torch.is_tensor(keys):
+        keys = list(keys)
+        if not keys:
+            raise SfError("byol_sim: no key views")
+        keys = keys[0].unsqueeze(0) if len(keys) == 1 else torch.stack(keys, 0)
+    return ByolSimFn.apply(p, keys.detach(), T)
 
 
 _err_words = {}
@@ -224,13 +291,23 @@ class Memory(nn.Module):
 def _check_cfg(cfg):
     c = cfg.CONTRASTIVE
     if c.TYPE in _UNSUPPORTED_TYPES:
-        raise NotImplementedError("CONTRASTIVE.TYPE %r: only \"moco\" runs on this engine" % (c.TYPE,))
-    if c.TYPE != "moco":
+        raise NotImplementedError("CONTRASTIVE.TYPE %r: only \"moco\" and \"byol\" run on this engine" % (c.TYPE,))
+    if c.TYPE not in ("moco", "byol"):
         raise NotImplementedError("CONTRASTIVE.TYPE %r" % (c.TYPE,))
-    if list(c.PREDICTOR_DEPTHS):
-        raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS: predictor heads belong to BYOL")
-    if c.BN_SYNC_MLP:
-        raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP: the MLP head's BatchNorm is per device")
+    if c.TYPE == "byol":
+        depths = list(c.PREDICTOR_DEPTHS)
+        if not depths:                      # the reference raises the same kind of error in forward (contrastive.py:514)
+            raise NotImplementedError("CONTRASTIVE.TYPE \"byol\": the predictor is missing (no depth in PREDICTOR_DEPTHS)")
+        if len(depths) != 1:                # the reference asserts len(predictors) == 1 in forward (:515)
+            raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS %r: BYOL takes exactly one predictor" % (depths,))
+        if c.BN_SYNC_MLP and (cfg.BN.NUM_SYNC_DEVICES != 1 or cfg.BN.GLOBAL_SYNC):
+            raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP with BN.NUM_SYNC_DEVICES %d, BN.GLOBAL_SYNC %s: the MLP heads' "
+                                      "BatchNorm is per device" % (cfg.BN.NUM_SYNC_DEVICES, bool(cfg.BN.GLOBAL_SYNC)))
+    else:
+        if list(c.PREDICTOR_DEPTHS):
+            raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS: predictor heads belong to BYOL")
+        if c.BN_SYNC_MLP:
+            raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP: the MLP head's BatchNorm is per device")
     if cfg.NUM_GPUS * cfg.NUM_SHARDS > 1:
         raise NotImplementedError("NUM_GPUS * NUM_SHARDS > 1: the cross-rank batch shuffle and key all-gather are not built")
     if cfg.MODEL.ARCH not in _MODEL_TYPES:
@@ -240,7 +317,9 @@ def _check_cfg(cfg):
 @MODEL_REGISTRY.register()
 class ContrastiveModel(nn.Module):
     """The reference's constructor, ``forward(clips, index, time, epoch_exact, keys)`` and state_dict (``backbone.*``,
-    ``backbone_hist.*``, ``ptr``, ``queue_x``, ``iter``, ``knn_mem.memory``) for ``CONTRASTIVE.TYPE == "moco"``."""
+    ``backbone_hist.*``, ``ptr``, ``queue_x``, ``iter``, ``knn_mem.memory``) for ``CONTRASTIVE.TYPE == "moco"`` and ``"byol"``
+    (the reference registers the queue buffers for byol too; with predictors the backbones' heads carry
+    ``head.predictors.0.projection.*``)."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -270,7 +349,8 @@ class ContrastiveModel(nn.Module):
         stdv = 1.0 / math.sqrt(self.dim / 3)
         self.register_buffer("queue_x", torch.rand(self.k, self.dim).mul_(2 * stdv).add_(-stdv))
         self.register_buffer("iter", torch.zeros([1], dtype=torch.long))
-        self._batch_shuffle_on = not ("sync" in cfg.BN.NORM_TYPE and cfg.BN.NUM_SYNC_DEVICES == cfg.NUM_GPUS)
+        self._batch_shuffle_on = not (("sync" in cfg.BN.NORM_TYPE and cfg.BN.NUM_SYNC_DEVICES == cfg.NUM_GPUS)
+                                      or self.type == "byol")
         if self.knn_on:
             self.knn_mem = Memory(self.length, 1, self.dim, cfg)
         # device-side step state that is no part of a checkpoint: the two momentum words and the enqueue's error word
@@ -404,7 +484,8 @@ class ContrastiveModel(nn.Module):
     def compute_key_feat(self, clips_k, compute_predictor_keys=False, batched_inference=True):
         assert self.training
         if compute_predictor_keys:
-            raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS: predictor keys belong to BYOL")
+            raise NotImplementedError("compute_predictor_keys=True: nothing in the reference calls it (both callers pass False), "
+                                      "and its batched branch slices a list of key matrices as if it were one")
         self._update_history()
         self.iter += 1
         self._iter_host += 1
@@ -427,8 +508,8 @@ class ContrastiveModel(nn.Module):
             # for a backward (the forward of every stage joins its own side streams; BatchNorm-partial tags are made by
             # backward nodes only)
             hist_feat = self.backbone_hist(clip_k)
-            if isinstance(hist_feat, list):
-                raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS")
+            if isinstance(hist_feat, list):         # [projection, predictor outputs]: the keys are the projection
+                hist_feat = hist_feat[0]
             # Normalize + _batch_unshuffle in one launch
             keys.append(l2norm_rows(hist_feat.float(), None if idx_restore is None else idx_restore[0]))
         if batched:
@@ -475,6 +556,8 @@ class ContrastiveModel(nn.Module):
     def forward(self, clips, index=None, time=None, epoch_exact=None, keys=None):
         if epoch_exact is not None and self.momentum_annealing:
             self.momentum_anneal_cosine(epoch_exact)
+        if self.type == "byol":
+            return self._forward_byol(clips, index, keys)
         if isinstance(clips[0], list):
             clip_q, clips_k = clips[0], list(clips[1:])
         else:
@@ -501,8 +584,56 @@ class ContrastiveModel(nn.Module):
         return logits, loss
 
 
+    def _forward_byol(self, clips, index, keys):
+        """The byol branch (contrastive.py:485-568).  Returns (dummy logits, loss); the dummy logits are a tensor shared between
+        calls (``dummy_logits``): callers must not write to it."""
+        many = isinstance(clips[0], list)
+        feat_q = self.backbone(clips[0] if many else clips)
+        if not isinstance(feat_q, list):
+            raise NotImplementedError("BYOL: predictor is missing")
+        assert len(feat_q) == 2, "BYOL takes exactly one predictor"
+        proj, pred = feat_q
+        if index is None:
+            return proj
+        if not self.training:
+            return self.eval_knn(l2norm_rows(proj.detach().float().contiguous()))
+        assert many, "training takes a list of clips"
+        if keys is None:
+            keys = self.compute_key_feat([list(clip) for clip in clips], compute_predictor_keys=False)
+        if self.cfg.CONTRASTIVE.SEQUENTIAL:
+            loss = byol_sim(pred.float(), keys, self.T)        # sum_v sim_loss(predictor, key_v) / V in one call
+        else:
+            assert len(clips) == 2, "the symmetric loss takes exactly two crops"
+            loss_q1 = byol_sim(pred.float(), [keys[1]], self.T)
+            feat_q2 = self.backbone(clips[1])
+            assert len(feat_q2) == 2
+            loss_q2 = byol_sim(feat_q2[1].float(), [keys[0]], self.T)
+            loss = loss_q1 + loss_q2
+        if self.knn_on:
+            self.knn_mem_update(l2norm_rows(proj.detach().float().contiguous()), index)
+        return dummy_logits(len(index), self.k, proj.device), loss
+
+
+_dummy_logits = {}
+
+
+def dummy_logits(rows, K, device):
+    """The (rows, 1 + K) matrix the byol branch returns in place of logits: 9999 in column 0, zeros elsewhere, so that the
+    training meter's top-1 reads 100 %.  Built once per (rows, K, device) -- 16.8 MB at the recipe's shapes, which the reference
+    allocates and fills twice per step -- and SHARED between calls: treat it as read-only (``torch.cat`` of it, as
+    ``contrastive_forward`` does, makes a new tensor)."""
+    key = (rows, K, torch.device(device))
+    t = _dummy_logits.get(key)
+    if t is None:
+        t = torch.zeros((rows, 1 + K), dtype=torch.float32, device=device)
+        t[:, 0] = 9999.0
+        _dummy_logits[key] = t
+    return t
+
+
 def contrastive_parameter_surgery(model, cfg, epoch_exact, cur_iter):
-    """contrastive.py:1031-1055 for moco: no parameter update while the queue fills during the first epoch."""
+    """contrastive.py:1031-1055: for moco no parameter update while the queue fills during the first epoch; byol updates from
+    the first iteration."""
     iters_noupdate = 0
     if cfg.MODEL.MODEL_NAME == "ContrastiveModel" and cfg.CONTRASTIVE.TYPE == "moco":
         assert cfg.CONTRASTIVE.QUEUE_LEN % (cfg.TRAIN.BATCH_SIZE * cfg.NUM_SHARDS) == 0
@@ -531,7 +662,8 @@ def contrastive_forward(model, cfg, inputs, index, time, epoch_exact, scaler=Non
                 preds = torch.cat([preds, lgt_k], dim=0)
                 partial_loss += loss_k.detach()
         partial_loss /= len(inputs) * 2.0       # to have same loss as symm model
-        mdl._dequeue_and_enqueue(keys)
+        if cfg.CONTRASTIVE.TYPE == "moco":      # byol keeps the queue buffers but never writes them (contrastive.py:1095)
+            mdl._dequeue_and_enqueue(keys)
     else:
         perform_backward = True
         preds, partial_loss = model(inputs, index, time, epoch_exact, keys=None)

@@ -26,6 +26,7 @@
 #include "sf_hog.h"
 #include "sf_pixel.h"
 #include "sf_moco.h"
+#include "sf_byol.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -3712,4 +3713,42 @@ extern "C" int sf_ema_update(int64_t n, const float* p_, float* hist, const floa
     p.vec = (uintptr_t)p_ % 16 == 0 && (uintptr_t)hist % 16 == 0;
     hipLaunchKernelGGL(sf_ema_update_kernel, dim3(sf_flat_blocks(n)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("ema_update");
+}
+
+// ================================================================================================
+// BYOL similarity loss (sf_byol.h; slowfast/models/contrastive.py: Normalize, sim_loss and the byol branch of forward).
+static int byol_check(const char* who, int32_t n, int32_t V, int32_t C) {
+    REQUIRE(n > 0, "%s: bad shape (n=%d)", who, n);
+    REQUIRE(V >= 1 && V <= SF_BYOL_VMAX, "%s: %d key views (1 .. %d)", who, V, SF_BYOL_VMAX);
+    REQUIRE(C >= 1 && C <= SF_BYOL_CMAX, "%s: C = %d: the feature dimension must be 1 .. %d", who, C, SF_BYOL_CMAX);
+    return 0;
+}
+extern "C" int64_t sf_byol_sim_workspace(int32_t n, int32_t V, int32_t C) {
+    if (byol_check("sf_byol_sim_workspace", n, V, C)) return -1;
+    return 4 * (int64_t)n;
+}
+static int byol_fill(const char* who, ByolSimParams& p, int32_t n, int32_t V, int32_t C, const float* x, int32_t ld,
+                     const float* key, float inv_T, float* df, float* loss, void* ws, int64_t ws_bytes) {
+    if (byol_check(who, n, V, C)) return -1;
+    REQUIRE(x && key && df && loss && ws, "%s: null pointer", who);
+    REQUIRE(ld >= C, "%s: row pitch %d below C = %d", who, ld, C);
+    REQUIRE(ws_bytes >= 4 * (int64_t)n, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes, 4ll * n);
+    p.p = x; p.key = key; p.df = df; p.loss = loss; p.ws = (float*)ws;
+    p.n = n; p.V = V; p.C = C; p.ld = ld; p.invT = inv_T;
+    p.coef = (float)(-(double)inv_T / ((double)V * (double)n));
+    return 0;
+}
+extern "C" int sf_byol_sim_rows(int32_t n, int32_t V, int32_t C, const float* x, int32_t ld, const float* key, float inv_T,
+                                float* df, float* loss, void* ws, int64_t ws_bytes, sf_stream_t stream) {
+    ByolSimParams p;
+    if (byol_fill("sf_byol_sim_rows", p, n, V, C, x, ld, key, inv_T, df, loss, ws, ws_bytes)) return -1;
+    hipLaunchKernelGGL(sf_byol_sim_rows_kernel, dim3(cdiv(n, SF_THREADS / 64)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("byol_sim_rows");
+}
+extern "C" int sf_byol_sim_finalize(int32_t n, int32_t V, int32_t C, const float* x, int32_t ld, const float* key, float inv_T,
+                                    float* df, float* loss, void* ws, int64_t ws_bytes, sf_stream_t stream) {
+    ByolSimParams p;
+    if (byol_fill("sf_byol_sim_finalize", p, n, V, C, x, ld, key, inv_T, df, loss, ws, ws_bytes)) return -1;
+    hipLaunchKernelGGL(sf_byol_sim_finalize_kernel, dim3(1), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("byol_sim_finalize");
 }

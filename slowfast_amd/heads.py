@@ -44,13 +44,16 @@ class _GlobalMeanFn(torch.autograd.Function):
 
 class MLPHead(nn.Module):
     """Projection MLP of the contrastive models (slowfast/models/head_helper.py:147-195): Linear [-> BatchNorm1d] -> ReLU ...
-    -> Linear; with ``bn_on`` only the last Linear has a bias.  Works on (N, C) features: plain torch ops, < 10 MMAC per clip."""
+    -> Linear; with ``bn_on`` only the last Linear has a bias.  Works on (N, C) features: plain torch ops, < 10 MMAC per clip.
+    ``bn_sync_num == 1`` without ``global_sync`` is what CONTRASTIVE.BN_SYNC_MLP comes to on one device: the reference builds a
+    plain BatchNorm1d then (head_helper.py:169-178); statistics shared between devices are not built."""
 
     def __init__(self, dim_in, dim_out, mlp_dim, num_layers, bn_on=False, bias=True, flatten=False, xavier_init=True,
                  bn_sync_num=1, global_sync=False):
         super().__init__()
         if global_sync or bn_sync_num > 1:
-            raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP: the MLP head's BatchNorm is per device")
+            raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP: the MLP head's BatchNorm is per device "
+                                      "(bn_sync_num=%d, global_sync=%s)" % (bn_sync_num, bool(global_sync)))
         self.flatten = flatten
         b = False if bn_on else bias
         mlp_layers = [nn.Linear(dim_in, mlp_dim, bias=b)]
@@ -58,6 +61,8 @@ class MLPHead(nn.Module):
         for i in range(1, num_layers):
             if bn_on:
                 mlp_layers.append(nn.BatchNorm1d(num_features=mlp_dim))
+                # torch's forward counts this layer's batches: the backbone's once-per-forward bump leaves it alone
+                mlp_layers[-1].__dict__["_sf_no_bump"] = True
             mlp_layers.append(nn.ReLU(inplace=True))
             if i == num_layers - 1:
                 d, b = dim_out, bias
@@ -83,21 +88,29 @@ class ResNetBasicHead(nn.Module):
         self.num_pathways = len(pool_size)
         self.detach_final_fc = detach_final_fc
         self.cfg = cfg
+        # BYOL's predictor MLPs on top of the projection (head_helper.py:288-303), registered where the reference registers
+        # them (in front of the pools and the projection: the order of state_dict()); empty for every other model
+        self.predictors = nn.ModuleList()
         for i, ps in enumerate(pool_size):
             pool = nn.AdaptiveAvgPool3d((1, 1, 1)) if ps is None else nn.AvgPool3d(tuple(ps), stride=1)
             self.add_module(f"pathway{i}_avgpool", pool)
         if dropout_rate > 0.0:
             self.dropout = nn.Dropout(dropout_rate)
         mlp_layers = cfg.CONTRASTIVE.NUM_MLP_LAYERS if cfg is not None else 1
+        # what CONTRASTIVE.BN_SYNC_MLP asks of the MLPs' BatchNorm (head_helper.py:270-273); contrastive._check_cfg is the gate
+        depths = list(cfg.CONTRASTIVE.PREDICTOR_DEPTHS) if cfg is not None else []
+        sync = {}
+        if mlp_layers != 1 or depths:
+            sync = dict(bn_sync_num=cfg.BN.NUM_SYNC_DEVICES if cfg.CONTRASTIVE.BN_SYNC_MLP else 1,
+                        global_sync=bool(cfg.CONTRASTIVE.BN_SYNC_MLP and cfg.BN.GLOBAL_SYNC))
         if mlp_layers == 1:
             self.projection = nn.Linear(sum(dim_in), num_classes, bias=True)
         else:                                   # the projection MLP of the contrastive models (head_helper.py:261-274)
-            if cfg.CONTRASTIVE.BN_SYNC_MLP:
-                raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP: the MLP head's BatchNorm is per device")
-            if list(cfg.CONTRASTIVE.PREDICTOR_DEPTHS):
-                raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS: predictor heads belong to BYOL")
             self.projection = MLPHead(sum(dim_in), num_classes, cfg.CONTRASTIVE.MLP_DIM, mlp_layers,
-                                      bn_on=cfg.CONTRASTIVE.BN_MLP)
+                                      bn_on=cfg.CONTRASTIVE.BN_MLP, **sync)
+        for depth in depths:
+            self.predictors.append(MLPHead(num_classes, num_classes, cfg.CONTRASTIVE.MLP_DIM, depth,
+                                           bn_on=cfg.CONTRASTIVE.BN_MLP, flatten=False, **sync))
         # (N, 1, 1, 1, C) -> (N, C) in front of the projection (head_helper.py:324-328): BatchNorm1d needs it
         self._flatten_pooled = cfg is not None and cfg.MODEL.MODEL_NAME == "ContrastiveModel"
         if act_func == "softmax":
@@ -132,12 +145,15 @@ class ResNetBasicHead(nn.Module):
         if self._flatten_pooled and tuple(x.shape[1:4]) == (1, 1, 1):
             x = x.view(x.shape[0], -1)
         x = self.projection(x)
+        # the predictors read the projection before the eval-mode activation (head_helper.py:332-336)
+        time_projs = [proj(x) for proj in self.predictors]
         if not self.training:
             if self.act is not None:
                 x = self.act(x)
             if x.dim() == 5:
                 x = x.mean([1, 2, 3])
-        return x.view(x.shape[0], -1)
+        x = x.view(x.shape[0], -1)
+        return [x] + time_projs if time_projs else x
 
 
 class _RoiPoolFn(torch.autograd.Function):
