@@ -2950,10 +2950,32 @@ extern "C" int sf_color_clip_f32(float* clip, int32_t N, int32_t T, int64_t HW, 
 }
 
 // ================================================================================================
+// The dense uint8 frame buffer (sf_u8frames.h) of the two stages below: its geometry, the choice of u8_walk's arm, a row's valid size.
+template <class P>
+static int fill_u8_frames(const char* who, P& p, const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_dev) {
+    REQUIRE(src && table_dev, "%s: null pointer", who);
+    REQUIRE(N > 0 && T > 0 && (int64_t)N * T <= 65535, "%s: bad shape (N * T must be 1 .. 65535)", who);
+    REQUIRE(Hs > 0 && Ws > 0 && Hs < (1 << 16) && Ws < (1 << 16) && (int64_t)Hs * Ws * 3 < (1ll << 31),
+            "%s: a frame of %d x %d is empty or has 2^31 bytes or more", who, Hs, Ws);
+    memset(&p, 0, sizeof(p));
+    p.src = (const unsigned char*)src; p.table = table_dev; p.N = N; p.T = T; p.Hs = Hs; p.Ws = Ws; p.slab = Hs * Ws;
+    p.fdW = make_fastdiv((uint32_t)Ws);
+    return 0;
+}
+// u8_walk's 16-byte arm: every frame slab starts on a 16-byte boundary in src and in dst (null: a pass that stores nothing)
+static int u8_frames_vec(const void* src, const void* dst, int slab) {
+    return (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 && slab % SF_U8_PIX == 0;
+}
+static int check_valid_size(const char* who, int n, int32_t h, int32_t w, int32_t Hs, int32_t Ws) {
+    REQUIRE(h > 0 && h <= Hs && w > 0 && w <= Ws, "%s: row %d: valid size %d x %d is not inside the %d x %d buffer", who, n, h, w, Hs, Ws);
+    return 0;
+}
+
+// ================================================================================================
 // RandAugment of the batch (sf_randaug.h; replaces the PIL loop of rand_augment_transform on the decoded frames,
 // datasets/kinetics.py:389-400).  One call is one LAYER of the draw: a table with a row per sample (layout: sf_randaug.h); the
 // HOST copy is validated and decides what is launched, the kernels read the device copy.  Kernel launches only.
-extern "C" int sf_randaug_chunk(void) { return SF_RANDAUG_CHUNK; }
+extern "C" int sf_randaug_chunk(void) { return SF_U8_CHUNK; }
 // counts the rows that need a histogram / a lookup table; -1 for a bad table
 static int check_randaug_table(const char* who, const int32_t* th, int32_t N, int32_t Hs, int32_t Ws, int& hist_rows, int& lut_rows) {
     REQUIRE(th, "%s: null table", who);
@@ -2967,8 +2989,7 @@ static int check_randaug_table(const char* who, const int32_t* th, int32_t N, in
         const bool is_affine = op == 3 || op == 11 || op == 12 || op == 13 || op == 14;
         REQUIRE(cls == 0 || (cls == 1 && is_lut) || (cls == 2 && op == 7) || (cls == 3 && op == 10) || (cls == 4 && is_affine),
                 "%s: row %d: op %d is not of class %d", who, n, op, cls);
-        REQUIRE(w[5] > 0 && w[5] <= Hs && w[6] > 0 && w[6] <= Ws, "%s: row %d: valid size %d x %d is not inside the %d x %d buffer",
-                who, n, w[5], w[6], Hs, Ws);
+        if (check_valid_size(who, n, w[5], w[6], Hs, Ws)) return -1;
         if (cls == 0) continue;
         REQUIRE(op != 4 || (w[2] >= 0 && w[2] <= 8), "%s: row %d: Posterize keeps 0 .. 8 bits (got %d)", who, n, w[2]);
         REQUIRE(op != 5 || (w[2] >= 0 && w[2] <= 256), "%s: row %d: Solarize takes a threshold of 0 .. 256 (got %d)", who, n, w[2]);
@@ -2984,30 +3005,19 @@ static int check_randaug_table(const char* who, const int32_t* th, int32_t N, in
     }
     return 0;
 }
-static int fill_randaug_params(const char* who, RandAugParams& p, const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
-                               const int32_t* table_dev) {
-    REQUIRE(src && table_dev, "%s: null pointer", who);
-    REQUIRE(N > 0 && T > 0 && (int64_t)N * T <= 65535, "%s: bad shape (N * T must be 1 .. 65535)", who);
-    REQUIRE(Hs > 0 && Ws > 0 && Hs < (1 << 16) && Ws < (1 << 16) && (int64_t)Hs * Ws * 3 < (1ll << 31),
-            "%s: a frame of %d x %d is empty or has 2^31 bytes or more", who, Hs, Ws);
-    memset(&p, 0, sizeof(p));
-    p.src = (const unsigned char*)src; p.table = table_dev; p.N = N; p.T = T; p.Hs = Hs; p.Ws = Ws; p.slab = Hs * Ws;
-    p.fdW = make_fastdiv((uint32_t)Ws);
-    return 0;
-}
 extern "C" int sf_randaug_hist_u8(const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
                                   const int32_t* table_dev, int32_t* hist, sf_stream_t stream) {
     RandAugParams p;
-    if (fill_randaug_params("sf_randaug_hist_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
+    if (fill_u8_frames("sf_randaug_hist_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
     int hist_rows, lut_rows;
     if (check_randaug_table("sf_randaug_hist_u8", table_host, N, Hs, Ws, hist_rows, lut_rows)) return -1;
     if (hist_rows == 0) return 0;                           // nothing to count: nothing is launched
     REQUIRE(hist && (uintptr_t)hist % 4 == 0, "sf_randaug_hist_u8: hist must be a 4-byte aligned pointer");
     p.hist = hist;
-    p.vec = (uintptr_t)src % 16 == 0 && p.slab % SF_RANDAUG_PIX == 0;
+    p.vec = u8_frames_vec(src, nullptr, p.slab);
     hipLaunchKernelGGL(sf_randaug_hist_zero_kernel, dim3(N * T), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     if (check_launch("randaug_hist_zero")) return -1;
-    hipLaunchKernelGGL(sf_randaug_hist_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
+    hipLaunchKernelGGL(sf_randaug_hist_kernel, dim3(cdiv(p.slab, SF_U8_CHUNK), N * T), dim3(SF_THREADS), 0,
                        (hipStream_t)stream, p);
     return check_launch("randaug_hist");
 }
@@ -3015,19 +3025,19 @@ extern "C" int sf_randaug_layer_u8(const void* src, void* dst, int32_t N, int32_
                                    const int32_t* table_host, const int32_t* table_dev, const int32_t* hist, void* lut,
                                    sf_stream_t stream) {
     RandAugParams p;
-    if (fill_randaug_params("sf_randaug_layer_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
+    if (fill_u8_frames("sf_randaug_layer_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
     REQUIRE(dst && dst != src, "sf_randaug_layer_u8: dst must be another buffer than src");
     int hist_rows, lut_rows;
     if (check_randaug_table("sf_randaug_layer_u8", table_host, N, Hs, Ws, hist_rows, lut_rows)) return -1;
     REQUIRE(hist_rows == 0 || hist, "sf_randaug_layer_u8: a row with AutoContrast, Equalize or Contrast needs the histograms");
     REQUIRE(lut_rows == 0 || lut, "sf_randaug_layer_u8: a row with a table op needs the table scratch");
     p.dst = (unsigned char*)dst; p.hist = const_cast<int32_t*>(hist); p.lut = (unsigned char*)lut;
-    p.vec = (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 && p.slab % SF_RANDAUG_PIX == 0;
+    p.vec = u8_frames_vec(src, dst, p.slab);
     if (lut_rows) {
         hipLaunchKernelGGL(sf_randaug_lut_kernel, dim3(N * T), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
         if (check_launch("randaug_lut")) return -1;
     }
-    hipLaunchKernelGGL(sf_randaug_stream_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
+    hipLaunchKernelGGL(sf_randaug_stream_kernel, dim3(cdiv(p.slab, SF_U8_CHUNK), N * T), dim3(SF_THREADS), 0,
                        (hipStream_t)stream, p);
     return check_launch("randaug_stream");
 }
@@ -3045,8 +3055,7 @@ static int check_sslcolor_table(const char* who, const int32_t* th, int32_t N, i
         const int32_t* w = th + (int64_t)n * SF_SSLCOLOR_ROW_WORDS;
         const int flags = w[0], order = w[1];
         REQUIRE(flags >= 0 && flags < 16, "%s: row %d: unknown flags %d", who, n, flags);
-        REQUIRE(w[9] > 0 && w[9] <= Hs && w[10] > 0 && w[10] <= Ws, "%s: row %d: valid size %d x %d is not inside the %d x %d buffer",
-                who, n, w[9], w[10], Hs, Ws);
+        if (check_valid_size(who, n, w[9], w[10], Hs, Ws)) return -1;
         if (flags & SF_SSLCOLOR_JITTER) {
             REQUIRE(order >= 0 && order < (1 << 16), "%s: row %d: the op order has more than four fields", who, n);
             int seen = 0;
@@ -3072,37 +3081,26 @@ static int check_sslcolor_table(const char* who, const int32_t* th, int32_t N, i
     }
     return 0;
 }
-static int fill_sslcolor_params(const char* who, SslColorParams& p, const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
-                                const int32_t* table_dev) {
-    REQUIRE(src && table_dev, "%s: null pointer", who);
-    REQUIRE(N > 0 && T > 0 && (int64_t)N * T <= 65535, "%s: bad shape (N * T must be 1 .. 65535)", who);
-    REQUIRE(Hs > 0 && Ws > 0 && Hs < (1 << 16) && Ws < (1 << 16) && (int64_t)Hs * Ws * 3 < (1ll << 31),
-            "%s: a frame of %d x %d is empty or has 2^31 bytes or more", who, Hs, Ws);
-    memset(&p, 0, sizeof(p));
-    p.src = (const unsigned char*)src; p.table = table_dev; p.N = N; p.T = T; p.Hs = Hs; p.Ws = Ws; p.slab = Hs * Ws;
-    p.fdW = make_fastdiv((uint32_t)Ws);
-    return 0;
-}
 extern "C" int sf_sslcolor_hist_u8(const void* src, int32_t N, int32_t T, int32_t Hs, int32_t Ws, const int32_t* table_host,
                                    const int32_t* table_dev, int32_t* hist, sf_stream_t stream) {
     SslColorParams p;
-    if (fill_sslcolor_params("sf_sslcolor_hist_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
+    if (fill_u8_frames("sf_sslcolor_hist_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
     int hist_rows, stream_rows, blur_rows;
     if (check_sslcolor_table("sf_sslcolor_hist_u8", table_host, N, Hs, Ws, hist_rows, stream_rows, blur_rows)) return -1;
     if (hist_rows == 0) return 0;                           // nothing to count: nothing is launched
     REQUIRE(hist && (uintptr_t)hist % 4 == 0, "sf_sslcolor_hist_u8: hist must be a 4-byte aligned pointer");
     p.hist = hist;
-    p.vec = (uintptr_t)src % 16 == 0 && p.slab % SF_RANDAUG_PIX == 0;
+    p.vec = u8_frames_vec(src, nullptr, p.slab);
     hipLaunchKernelGGL(sf_sslcolor_hist_zero_kernel, dim3(N), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     if (check_launch("sslcolor_hist_zero")) return -1;
-    hipLaunchKernelGGL(sf_sslcolor_hist_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
+    hipLaunchKernelGGL(sf_sslcolor_hist_kernel, dim3(cdiv(p.slab, SF_U8_CHUNK), N * T), dim3(SF_THREADS), 0,
                        (hipStream_t)stream, p);
     return check_launch("sslcolor_hist");
 }
 extern "C" int sf_sslcolor_stream_u8(const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
                                      const int32_t* table_host, const int32_t* table_dev, const int32_t* hist, sf_stream_t stream) {
     SslColorParams p;
-    if (fill_sslcolor_params("sf_sslcolor_stream_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
+    if (fill_u8_frames("sf_sslcolor_stream_u8", p, src, N, T, Hs, Ws, table_dev)) return -1;
     const int64_t bytes = (int64_t)N * T * p.slab * 3;
     REQUIRE(dst, "sf_sslcolor_stream_u8: null dst");
     REQUIRE(dst == src || (const unsigned char*)dst + bytes <= (const unsigned char*)src || (const unsigned char*)src + bytes <= (const unsigned char*)dst,
@@ -3112,15 +3110,15 @@ extern "C" int sf_sslcolor_stream_u8(const void* src, void* dst, int32_t N, int3
     REQUIRE(hist_rows == 0 || hist, "sf_sslcolor_stream_u8: a row with contrast needs the histograms");
     if (stream_rows == 0 && dst == src) return 0;           // in place and nothing drawn: nothing is launched
     p.dst = (unsigned char*)dst; p.hist = const_cast<int32_t*>(hist);
-    p.vec = (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 && p.slab % SF_RANDAUG_PIX == 0;
-    hipLaunchKernelGGL(sf_sslcolor_stream_kernel, dim3(cdiv(p.slab, SF_RANDAUG_CHUNK), N * T), dim3(SF_THREADS), 0,
+    p.vec = u8_frames_vec(src, dst, p.slab);
+    hipLaunchKernelGGL(sf_sslcolor_stream_kernel, dim3(cdiv(p.slab, SF_U8_CHUNK), N * T), dim3(SF_THREADS), 0,
                        (hipStream_t)stream, p);
     return check_launch("sslcolor_stream");
 }
 static int sslcolor_blur(const char* who, bool cols, const void* src, void* dst, int32_t N, int32_t T, int32_t Hs, int32_t Ws,
                          const int32_t* table_host, const int32_t* table_dev, sf_stream_t stream) {
     SslColorParams p;
-    if (fill_sslcolor_params(who, p, src, N, T, Hs, Ws, table_dev)) return -1;
+    if (fill_u8_frames(who, p, src, N, T, Hs, Ws, table_dev)) return -1;
     const int64_t bytes = (int64_t)N * T * p.slab * 3;
     REQUIRE(dst && ((const unsigned char*)dst + bytes <= (const unsigned char*)src || (const unsigned char*)src + bytes <= (const unsigned char*)dst),
             "%s: dst must be another buffer than src", who);

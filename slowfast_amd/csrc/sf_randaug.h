@@ -24,12 +24,10 @@
 //              trigonometry here
 //
 // Arithmetic (PIL's observable behaviour; every floating-point expression WITHOUT contraction):
-//     L(p)        = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16
-//     blend(d,v,f): t = (float)d + f * (float)(v - d) in fp32, product rounded, then sum rounded; 0 <= f <= 1: trunc(t);
-//                   otherwise t <= 0 -> 0, t >= 255 -> 255, else trunc(t)
+//     L(p), blend(d, v, f) and the mean of a 256-bin table: sf_u8frames.h
 //     Brightness  blend(0, v, f)                                                          (table)
 //     Color       blend(L(p), v, f) per channel
-//     Contrast    m = trunc(sum_i i * histL[i] / count + 0.5) (exact integer sum, fp64 division); blend(m, v, f)    (table)
+//     Contrast    blend(m, v, f), m the mean of the frame's L table                       (table)
 //     Sharpness   s = (2 * acc + 13) / 26 in integers, acc the 3 x 3 sum with the centre weighted 5; the one-pixel border of
 //                 the VALID region takes s = v; blend(s, v, f)
 //     Invert 255 - v;  Solarize v < th ? v : 255 - v;  SolarizeAdd v < 128 ? min(255, v + add) : v;
@@ -46,63 +44,35 @@
 //                           p3 = 2*(v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4, v = p1 + d*(p2 + d*(p3 + d*p4)), rows first,
 //                           then the four row results in y; v <= 0 -> 0, v >= 255 -> 255, else trunc (NOT rounded)
 //
-// What a thread owns.  A frame's slab of Hs * Ws pixels is cut into chunks of SF_RANDAUG_CHUNK pixels, one workgroup each;
-// the workgroup reads its sample's row and branches uniformly.  The pointwise classes (copy, table, Color) take 16 adjacent
-// pixels per thread -- 48 bytes, three 16-byte accesses -- when every frame slab starts on a 16-byte boundary (Hs * Ws % 16 == 0
-// and aligned bases); otherwise, and for the gathering classes (Sharpness, affine), thread t takes pixels t, t + 256, ... of the
-// chunk, so a wave's byte accesses are adjacent.  A gather fetches the adjacent taps of one row (3 x 3 bytes for Sharpness, 2 x 3 /
-// 4 x 3 for bilinear / bicubic) as one unaligned block when all of them lie inside the valid region, tap by tap with clamped
-// columns otherwise.  Source coordinates are clamped to the valid region before every load: nothing reads outside the sample's
-// slab.
-//
-// Histograms: integer LDS counters, one set per wave (16 KiB per workgroup) so that the four waves do not serialise on the
-// few bins a natural frame fills, merged into the frame's table with integer atomic adds of the non-empty bins: the result
-// does not depend on the order, two calls give the same bits.
+// What a thread owns: sf_u8frames.h -- the chunks of a frame's slab, the 16-byte and the per-pixel arm, and what the walk
+// guarantees.  The pointwise classes (copy, table, Color) take the 16-byte arm when the slabs are aligned; the gathering classes
+// (Sharpness, affine) always take the per-pixel arm and need dst != src.  A gather fetches the adjacent taps of one row (3 x 3
+// bytes for Sharpness, 2 x 3 / 4 x 3 for bilinear / bicubic) as one unaligned block when all of them lie inside the valid region,
+// tap by tap with clamped columns otherwise.  Source coordinates are clamped to the valid region before every load: nothing reads
+// outside the sample's slab.  Histograms: the per-wave LDS counters of sf_u8frames.h, four tables (R, G, B, L) per wave.
 #pragma once
 #include "sf_common.h"
+#include "sf_u8frames.h"
 
 #define SF_RANDAUG_ROW_WORDS 20
-#define SF_RANDAUG_PIX 16                                   // pixels per thread
-#define SF_RANDAUG_CHUNK (SF_THREADS * SF_RANDAUG_PIX)      // pixels per workgroup: 4096
 #define SF_RANDAUG_OPS 15
 
 static_assert(SF_THREADS == 256, "the table kernel builds entry threadIdx.x of a 256-entry table");
 
-typedef uint32_t ra_u32x4 __attribute__((ext_vector_type(4)));
-
-struct RandAugParams {
-    const unsigned char* src;   // [N][T][Hs][Ws][3]
-    unsigned char* dst;         // the same shape, another buffer
+struct RandAugParams : U8Frames {   // dst: another buffer than src
     const int32_t* table;       // device copy: the layer's N rows
     int* hist;                  // [N * T][4][256]: R, G, B, L
     unsigned char* lut;         // [N * T][3][256]
-    int N, T, Hs, Ws;
-    int slab;                   // Hs * Ws
-    int vec;                    // every frame slab is 16-byte aligned in src and dst
-    FastDiv fdW;                // Ws
 };
 
 __host__ __device__ __forceinline__ bool randaug_needs_hist(int cls, int op) {
     return cls == 1 && (op == 0 || op == 1 || op == 8);
-}
-__device__ __forceinline__ int randaug_luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
-__device__ __forceinline__ int randaug_blend(int d, int v, float f) {
-#pragma clang fp contract(off)
-    const float prod = f * (float)(v - d);
-    const float t = (float)d + prod;
-    if (f >= 0.0f && f <= 1.0f) return (int)t;
-    return t <= 0.0f ? 0 : (t >= 255.0f ? 255 : (int)t);
 }
 __device__ __forceinline__ double randaug_f64(const int32_t* w) {
     const uint64_t bits = (uint64_t)(uint32_t)w[0] | ((uint64_t)(uint32_t)w[1] << 32);
     double d;
     __builtin_memcpy(&d, &bits, 8);
     return d;
-}
-__device__ __forceinline__ float randaug_f32(int32_t w) {
-    float f;
-    __builtin_memcpy(&f, &w, 4);
-    return f;
 }
 
 // ---- histograms: grid (chunks, N * T) ------------------------------------------------------------------------------------
@@ -120,62 +90,15 @@ __global__ __launch_bounds__(SF_THREADS) void sf_randaug_hist_kernel(RandAugPara
     const int32_t* row = p.table + (int64_t)(frame / p.T) * SF_RANDAUG_ROW_WORDS;
     if (!randaug_needs_hist(row[0], row[1])) return;        // the whole workgroup
     const int h = row[5], w = row[6];
-    const int p0 = blockIdx.x * SF_RANDAUG_CHUNK;
-    if (p0 >= h * p.Ws) return;                             // the chunk lies below the valid rows
-    for (int i = threadIdx.x; i < (SF_THREADS / 64) * 1024; i += SF_THREADS) (&s_h[0][0][0])[i] = 0;
-    __syncthreads();
-    int (*mine)[256] = s_h[threadIdx.x >> 6];
-    const unsigned char* base = p.src + (int64_t)frame * p.slab * 3;
-    if (p.vec) {
-        const int q = p0 + threadIdx.x * SF_RANDAUG_PIX;    // slab % 16 == 0: a group is inside the slab or outside as a whole
-        if (q < p.slab) {
-            uint32_t v[12];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const ra_u32x4 in = *reinterpret_cast<const ra_u32x4*>(base + (int64_t)q * 3 + 16 * k);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 * k + e] = in[e];
-            }
-            uint32_t y, x;
-            fd_divmod((uint32_t)q, p.fdW, y, x);
-#pragma unroll
-            for (int e = 0; e < SF_RANDAUG_PIX; ++e) {
-                if ((int)y < h && (int)x < w) {
-                    int c[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) c[k] = (v[(3 * e + k) >> 2] >> (8 * ((3 * e + k) & 3))) & 255u;
-                    atomicAdd(&mine[0][c[0]], 1);
-                    atomicAdd(&mine[1][c[1]], 1);
-                    atomicAdd(&mine[2][c[2]], 1);
-                    atomicAdd(&mine[3][randaug_luma(c[0], c[1], c[2])], 1);
-                }
-                if ((int)++x == p.Ws) { x = 0; ++y; }
-            }
-        }
-    } else {
-        for (int k = 0; k < SF_RANDAUG_PIX; ++k) {
-            const int q = p0 + k * SF_THREADS + threadIdx.x;
-            if (q >= p.slab) break;
-            uint32_t y, x;
-            fd_divmod((uint32_t)q, p.fdW, y, x);
-            if ((int)y >= h || (int)x >= w) continue;
-            const unsigned char* px = base + (int64_t)q * 3;
-            const int r = px[0], g = px[1], b = px[2];
-            atomicAdd(&mine[0][r], 1);
-            atomicAdd(&mine[1][g], 1);
-            atomicAdd(&mine[2][b], 1);
-            atomicAdd(&mine[3][randaug_luma(r, g, b)], 1);
-        }
-    }
-    __syncthreads();
-    int* out = p.hist + (int64_t)frame * 1024;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        int s = 0;
-#pragma unroll
-        for (int wv = 0; wv < SF_THREADS / 64; ++wv) s += s_h[wv][c][threadIdx.x];
-        if (s) atomicAdd(&out[c * 256 + threadIdx.x], s);
-    }
+    if ((int)blockIdx.x * SF_U8_CHUNK >= h * p.Ws) return;  // the chunk lies below the valid rows
+    u8_hist_clear(s_h);
+    u8_walk<false>(p, frame, blockIdx.x, h, w, p.vec, [=](int (&c)[3], int, int) {
+        u8_hist_count(s_h, 0, c[0]);
+        u8_hist_count(s_h, 1, c[1]);
+        u8_hist_count(s_h, 2, c[2]);
+        u8_hist_count(s_h, 3, u8_luma(c[0], c[1], c[2]));
+    });
+    u8_hist_merge(s_h, p.hist + (int64_t)frame * 1024);
 }
 
 // ---- lookup tables: grid N * T, thread i builds entry i of the three channels ----------------------------------------------
@@ -186,7 +109,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_randaug_lut_kernel(RandAugParam
     const int32_t* row = p.table + (int64_t)(frame / p.T) * SF_RANDAUG_ROW_WORDS;
     if (row[0] != 1) return;                                // the whole workgroup
     const int op = row[1], iarg = row[2], i = threadIdx.x;
-    const float f = randaug_f32(row[3]);
+    const float f = u8_f32(row[3]);
     int out[3] = {i, i, i};
     if (randaug_needs_hist(1, op)) {
         const int* h = p.hist + (int64_t)frame * 1024;
@@ -204,16 +127,9 @@ __global__ __launch_bounds__(SF_THREADS) void sf_randaug_lut_kernel(RandAugParam
     } else if (op == 6) {
         out[0] = out[1] = out[2] = i < 128 ? (i + iarg > 255 ? 255 : i + iarg) : i;
     } else if (op == 9) {
-        out[0] = out[1] = out[2] = randaug_blend(0, i, f);
+        out[0] = out[1] = out[2] = u8_blend(0, i, f);
     } else if (op == 8) {
-        int64_t sum = 0, count = 0;
-        for (int k = 0; k < 256; ++k) {
-            sum += (int64_t)k * s_h[3][k];
-            count += s_h[3][k];
-        }
-        const double mean = (double)sum / (double)count;
-        const int m = (int)(mean + 0.5);
-        out[0] = out[1] = out[2] = randaug_blend(m, i, f);
+        out[0] = out[1] = out[2] = u8_blend(u8_hist_mean(s_h[3]), i, f);
     } else if (op == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -317,7 +233,7 @@ __device__ __forceinline__ void randaug_sharpness(const unsigned char* base, int
         }
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) out[c] = randaug_blend(border ? in[c] : (2 * acc[c] + 13) / 26, in[c], f);
+    for (int c = 0; c < 3; ++c) out[c] = u8_blend(border ? in[c] : (2 * acc[c] + 13) / 26, in[c], f);
 }
 // the affine gather at output pixel (x, y) of the valid region
 __device__ __forceinline__ void randaug_affine(const unsigned char* base, int Ws, int w, int h, int x, int y, const double (&a)[6],
@@ -375,93 +291,39 @@ __global__ __launch_bounds__(SF_THREADS) void sf_randaug_stream_kernel(RandAugPa
     const int frame = blockIdx.y;
     const int32_t* row = p.table + (int64_t)(frame / p.T) * SF_RANDAUG_ROW_WORDS;
     const int cls = row[0], h = row[5], w = row[6];
-    const float f = randaug_f32(row[3]);
-    const unsigned char* base = p.src + (int64_t)frame * p.slab * 3;
-    unsigned char* obase = p.dst + (int64_t)frame * p.slab * 3;
-    const int p0 = blockIdx.x * SF_RANDAUG_CHUNK;
+    const float f = u8_f32(row[3]);
     if (cls == 1) {                                         // uniform: the whole workgroup reaches the barrier
         const unsigned char* lut = p.lut + (int64_t)frame * 768;
         for (int i = threadIdx.x; i < 768; i += SF_THREADS) s_lut[i] = lut[i];
         __syncthreads();
     }
-    if (cls <= 2 && p.vec) {
-        const int q = p0 + threadIdx.x * SF_RANDAUG_PIX;    // slab % 16 == 0: a group is inside the slab or outside as a whole
-        if (q >= p.slab) return;
-        uint32_t v[12], o[12];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const ra_u32x4 in = *reinterpret_cast<const ra_u32x4*>(base + (int64_t)q * 3 + 16 * k);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[4 * k + e] = in[e];
-        }
-        if (cls == 0) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o[k] = v[k];
-        } else {
-            uint32_t y, x;
-            fd_divmod((uint32_t)q, p.fdW, y, x);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o[k] = 0;
-#pragma unroll
-            for (int e = 0; e < SF_RANDAUG_PIX; ++e) {
-                int c[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) c[k] = (v[(3 * e + k) >> 2] >> (8 * ((3 * e + k) & 3))) & 255u;
-                if ((int)y < h && (int)x < w) {
-                    if (cls == 1) {
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) c[k] = s_lut[k * 256 + c[k]];
-                    } else {
-                        const int l = randaug_luma(c[0], c[1], c[2]);
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) c[k] = randaug_blend(l, c[k], f);
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 3; ++k) o[(3 * e + k) >> 2] |= (uint32_t)c[k] << (8 * ((3 * e + k) & 3));
-                if ((int)++x == p.Ws) { x = 0; ++y; }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            ra_u32x4 st;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) st[e] = o[4 * k + e];
-            *reinterpret_cast<ra_u32x4*>(obase + (int64_t)q * 3 + 16 * k) = st;
-        }
-        return;
-    }
-    double a[6] = {0, 0, 0, 0, 0, 0};
-    if (cls == 4) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) a[k] = randaug_f64(row + 8 + 2 * k);
-    }
-    const int filter = row[4];
-    for (int k = 0; k < SF_RANDAUG_PIX; ++k) {
-        const int q = p0 + k * SF_THREADS + threadIdx.x;
-        if (q >= p.slab) break;
-        uint32_t y, x;
-        fd_divmod((uint32_t)q, p.fdW, y, x);
-        const unsigned char* px = base + (int64_t)q * 3;
-        const int in[3] = {px[0], px[1], px[2]};
-        int out[3] = {in[0], in[1], in[2]};
-        if ((int)y < h && (int)x < w) {
+    if (cls <= 2) {                                         // pointwise; class 0 is a copy: an empty valid region
+        u8_walk<true>(p, frame, blockIdx.x, cls == 0 ? 0 : h, w, p.vec, [=](int (&c)[3], int, int) {
             if (cls == 1) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) out[c] = s_lut[c * 256 + in[c]];
-            } else if (cls == 2) {
-                const int l = randaug_luma(in[0], in[1], in[2]);
+                for (int k = 0; k < 3; ++k) c[k] = s_lut[k * 256 + c[k]];
+            } else {
+                const int l = u8_luma(c[0], c[1], c[2]);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) out[c] = randaug_blend(l, in[c], f);
-            } else if (cls == 3) {
-                randaug_sharpness(base, p.Ws, w, h, (int)x, (int)y, f, in, out);
-            } else if (cls == 4) {
-                randaug_affine(base, p.Ws, w, h, (int)x, (int)y, a, filter, out);
+                for (int k = 0; k < 3; ++k) c[k] = u8_blend(l, c[k], f);
             }
-        }
-        unsigned char* po = obase + (int64_t)q * 3;
-        po[0] = (unsigned char)out[0];
-        po[1] = (unsigned char)out[1];
-        po[2] = (unsigned char)out[2];
+        });
+        return;
     }
+    // Sharpness and the affine ops (class 4: the launcher admits 0 .. 4) gather from their neighbours in src: the per-pixel arm,
+    // dst != src (the launcher checks).  A walk per class: one loop around both gathers costs the kernel a wave per SIMD.
+    const unsigned char* base = p.src + (int64_t)frame * p.slab * 3;
+    if (cls == 3) {
+        u8_walk<true>(p, frame, blockIdx.x, h, w, false, [=](int (&c)[3], int x, int y) {
+            const int in[3] = {c[0], c[1], c[2]};
+            randaug_sharpness(base, p.Ws, w, h, x, y, f, in, c);
+        });
+        return;
+    }
+    double a[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a[k] = randaug_f64(row + 8 + 2 * k);
+    const int filter = row[4];
+    u8_walk<true>(p, frame, blockIdx.x, h, w, false,
+                  [=](int (&c)[3], int x, int y) { randaug_affine(base, p.Ws, w, h, x, y, a, filter, c); });
 }

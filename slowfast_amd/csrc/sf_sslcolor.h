@@ -1,7 +1,7 @@
 // SSL colour augmentation of a training batch on the device (transform.color_jitter_video_ssl, slowfast/datasets/transform.py:
 // 1073-1121 with GaussianBlur at :1145-1157, applied at datasets/kinetics.py:378-387 to the decoded uint8 frames).  The draw stays
 // on the host (slowfast_amd/ssl_color.py) and arrives as ONE table with a row per clip; the frames are the dense uint8
-// [N][T][Hs][Ws][3] buffer of sf_randaug.h (RGB byte order), of which sample n uses the h x w corner its row names.  The reference
+// [N][T][Hs][Ws][3] buffer of sf_u8frames.h (RGB byte order), of which sample n uses the h x w corner its row names.  The reference
 // hands PIL ONE image per clip, the (T * h) x w stack of its frames: a statistic (Contrast's mean) is the clip's, and the blur's
 // column passes run across the frame seams.  Inside the valid region the bytes are PIL's, bit for bit; outside it they are
 // copied.
@@ -23,9 +23,10 @@
 //     [9],[10] h, w: the valid size of the sample's frames
 //     [11..15] 0
 //
-// Arithmetic (PIL's observable behaviour; every floating-point expression WITHOUT contraction).  L and blend(d, v, f): sf_randaug.h.
-//     brightness  blend(0, v, f);  contrast  blend(m, v, f), m = trunc(sum_i i * histL[i] / count + 0.5) over the CLIP's T * h * w
-//                 pixels (exact integer sum, fp64 division);  saturation  blend(L(p), v, f);  grey  (L(p), L(p), L(p))
+// Arithmetic (PIL's observable behaviour; every floating-point expression WITHOUT contraction).  L, blend(d, v, f) and the mean of a
+// 256-bin table: sf_u8frames.h.
+//     brightness  blend(0, v, f);  contrast  blend(m, v, f), m the mean of L over the CLIP's T * h * w pixels;
+//                 saturation  blend(L(p), v, f);  grey  (L(p), L(p), L(p))
 //     hue         RGB -> HSV, H = (H + shift) & 255, HSV -> RGB
 //       RGB->HSV  V = max; max == min: H = S = 0.  else in fp32: cr = max - min, s = cr / max, rc = (max - r) / cr, gc, bc alike;
 //                 r == max: hh = bc - gc (fp32); else g == max: hh = (float)(2.0 + rc - bc) (fp64 sum, left to right); else
@@ -39,18 +40,17 @@
 //                 clamp to 0 .. n - 1; three iterations along the rows (n = w), then three along the columns of the stack
 //                 (n = T * h: replication only at the first row of frame 0 and the last row of frame T - 1), each rounding to uint8
 //
-// What a thread owns.  Histogram and streaming pass: sf_randaug.h's chunks of SF_RANDAUG_CHUNK pixels of a frame, 16 adjacent
-// pixels (three 16-byte accesses) per thread when every frame slab starts on a 16-byte boundary, thread-per-pixel otherwise.  The
-// streaming pass may run in place (dst == src): a thread reads its pixels before it writes them.  Row blur: a workgroup owns
-// `rows` adjacent rows of a clip's stack (rows * 3 * w <= SF_SSLCOLOR_ROW_LDS bytes), SF_THREADS / rows threads walk a row byte by
-// byte, two LDS buffers ping-pong.  Column blur: a workgroup owns SF_SSLCOLOR_COLS columns x SF_SSLCOLOR_RUN stacked rows plus
-// SF_SSLCOLOR_HALO rows on either side, a thread four adjacent bytes (one dword) of a tile row; every
-// iteration is computed for the whole tile with the taps clamped to the stack first and to the tile second, so what is wrong
-// near the tile's edge after iteration k lies within k * (r + 1) <= 6 rows of it and never reaches the rows that are stored.
-// Clips without the pass's flag leave at once.  Histograms: per-wave LDS counters merged with integer atomic adds.
+// What a thread owns.  Histogram and streaming pass: sf_u8frames.h; every op is pointwise, so the streaming pass may run in place
+// (dst == src).  Row blur: a workgroup owns `rows` adjacent rows of a clip's stack (rows * 3 * w <= SF_SSLCOLOR_ROW_LDS bytes),
+// SF_THREADS / rows threads walk a row byte by byte, two LDS buffers ping-pong.  Column blur: a workgroup owns SF_SSLCOLOR_COLS
+// columns x SF_SSLCOLOR_RUN stacked rows plus SF_SSLCOLOR_HALO rows on either side, a thread four adjacent bytes (one dword) of a
+// tile row; every iteration is computed for the whole tile with the taps clamped to the stack first and to the tile second, so
+// what is wrong near the tile's edge after iteration k lies within k * (r + 1) <= 6 rows of it and never reaches the rows that are
+// stored.  Clips without the pass's flag leave at once.  Histograms: the per-wave LDS counters of sf_u8frames.h, one table (L)
+// per wave.
 #pragma once
 #include "sf_common.h"
-#include "sf_randaug.h"
+#include "sf_u8frames.h"
 
 #define SF_SSLCOLOR_ROW_WORDS 16
 #define SF_SSLCOLOR_JITTER 1
@@ -66,17 +66,10 @@
 #define SF_SSLCOLOR_HALO 6              // 3 iterations x (r + 1), r <= 1
 #define SF_SSLCOLOR_TILE_ROWS (SF_SSLCOLOR_RUN + 2 * SF_SSLCOLOR_HALO)
 
-struct SslColorParams {
-    const unsigned char* src;   // [N][T][Hs][Ws][3]
-    unsigned char* dst;         // the same shape
+struct SslColorParams : U8Frames {  // vec, column blur: every row of every frame is 4-byte aligned in src and dst
     const int32_t* table;       // device copy: N rows
     int* hist;                  // [N][256]: L of the clip
-    int N, T, Hs, Ws;
-    int slab;                   // Hs * Ws
-    int vec;                    // histogram, streaming pass: every frame slab is 16-byte aligned in src and dst; column blur:
-                                // every row of every frame is 4-byte aligned in both
     int rows;                   // row blur: stacked rows per workgroup
-    FastDiv fdW;                // Ws
 };
 
 // the row's jitter draws contrast
@@ -94,7 +87,7 @@ struct SslColorRow {
 __device__ __forceinline__ SslColorRow sslcolor_row(const int32_t* row) {
     SslColorRow r;
     r.flags = row[0]; r.order = row[1]; r.shift = row[5];
-    r.fb = randaug_f32(row[2]); r.fc = randaug_f32(row[3]); r.fs = randaug_f32(row[4]);
+    r.fb = u8_f32(row[2]); r.fc = u8_f32(row[3]); r.fs = u8_f32(row[4]);
     return r;
 }
 
@@ -162,7 +155,7 @@ __device__ __forceinline__ void sslcolor_hsv2rgb(int h, int s, int v, int (&c)[3
         default: c[0] = v; c[1] = p; c[2] = q; break;
     }
 }
-__device__ __forceinline__ void sslcolor_grey(int (&c)[3]) { c[0] = c[1] = c[2] = randaug_luma(c[0], c[1], c[2]); }
+__device__ __forceinline__ void sslcolor_grey(int (&c)[3]) { c[0] = c[1] = c[2] = u8_luma(c[0], c[1], c[2]); }
 
 // one pixel through the row.  PRE: only what precedes contrast (the histogram pass); mean: Contrast's degenerate value
 template <bool PRE>
@@ -173,15 +166,15 @@ __device__ __forceinline__ void sslcolor_pixel(int (&c)[3], const SslColorRow& r
             const int op = (r.order >> (4 * k)) & 15;
             if (op == 0) {
 #pragma unroll
-                for (int j = 0; j < 3; ++j) c[j] = randaug_blend(0, c[j], r.fb);
+                for (int j = 0; j < 3; ++j) c[j] = u8_blend(0, c[j], r.fb);
             } else if (op == 1) {
                 if (PRE) return;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) c[j] = randaug_blend(mean, c[j], r.fc);
+                for (int j = 0; j < 3; ++j) c[j] = u8_blend(mean, c[j], r.fc);
             } else if (op == 2) {
-                const int l = randaug_luma(c[0], c[1], c[2]);
+                const int l = u8_luma(c[0], c[1], c[2]);
 #pragma unroll
-                for (int j = 0; j < 3; ++j) c[j] = randaug_blend(l, c[j], r.fs);
+                for (int j = 0; j < 3; ++j) c[j] = u8_blend(l, c[j], r.fs);
             } else if (op == 3) {
                 int h, s, v;
                 sslcolor_rgb2hsv(c[0], c[1], c[2], h, s, v);
@@ -200,66 +193,24 @@ __global__ __launch_bounds__(SF_THREADS) void sf_sslcolor_hist_zero_kernel(SslCo
     p.hist[(int64_t)blockIdx.x * 256 + threadIdx.x] = 0;
 }
 __global__ __launch_bounds__(SF_THREADS) void sf_sslcolor_hist_kernel(SslColorParams p) {
-    __shared__ int s_h[SF_THREADS / 64][256];
+    __shared__ int s_h[SF_THREADS / 64][1][256];
     const int frame = blockIdx.y;
     const int n = frame / p.T;
     const int32_t* row = p.table + (int64_t)n * SF_SSLCOLOR_ROW_WORDS;
     if (!sslcolor_needs_hist(row[0], row[1])) return;       // the whole workgroup
     const SslColorRow r = sslcolor_row(row);
     const int h = row[9], w = row[10];
-    const int p0 = blockIdx.x * SF_RANDAUG_CHUNK;
-    if (p0 >= h * p.Ws) return;                             // the chunk lies below the valid rows
-    for (int i = threadIdx.x; i < (SF_THREADS / 64) * 256; i += SF_THREADS) (&s_h[0][0])[i] = 0;
-    __syncthreads();
-    int* mine = s_h[threadIdx.x >> 6];
-    const unsigned char* base = p.src + (int64_t)frame * p.slab * 3;
-    if (p.vec) {
-        const int q = p0 + threadIdx.x * SF_RANDAUG_PIX;    // slab % 16 == 0: a group is inside the slab or outside as a whole
-        if (q < p.slab) {
-            uint32_t v[12];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const ra_u32x4 in = *reinterpret_cast<const ra_u32x4*>(base + (int64_t)q * 3 + 16 * k);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 * k + e] = in[e];
-            }
-            uint32_t y, x;
-            fd_divmod((uint32_t)q, p.fdW, y, x);
-#pragma unroll
-            for (int e = 0; e < SF_RANDAUG_PIX; ++e) {
-                if ((int)y < h && (int)x < w) {
-                    int c[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) c[k] = (v[(3 * e + k) >> 2] >> (8 * ((3 * e + k) & 3))) & 255u;
-                    sslcolor_pixel<true>(c, r, 0);
-                    atomicAdd(&mine[randaug_luma(c[0], c[1], c[2])], 1);
-                }
-                if ((int)++x == p.Ws) { x = 0; ++y; }
-            }
-        }
-    } else {
-        for (int k = 0; k < SF_RANDAUG_PIX; ++k) {
-            const int q = p0 + k * SF_THREADS + threadIdx.x;
-            if (q >= p.slab) break;
-            uint32_t y, x;
-            fd_divmod((uint32_t)q, p.fdW, y, x);
-            if ((int)y >= h || (int)x >= w) continue;
-            const unsigned char* px = base + (int64_t)q * 3;
-            int c[3] = {px[0], px[1], px[2]};
-            sslcolor_pixel<true>(c, r, 0);
-            atomicAdd(&mine[randaug_luma(c[0], c[1], c[2])], 1);
-        }
-    }
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int wv = 0; wv < SF_THREADS / 64; ++wv) s += s_h[wv][threadIdx.x];
-    if (s) atomicAdd(&p.hist[(int64_t)n * 256 + threadIdx.x], s);
+    if ((int)blockIdx.x * SF_U8_CHUNK >= h * p.Ws) return;  // the chunk lies below the valid rows
+    u8_hist_clear(s_h);
+    u8_walk<false>(p, frame, blockIdx.x, h, w, p.vec, [=](int (&c)[3], int, int) {
+        sslcolor_pixel<true>(c, r, 0);
+        u8_hist_count(s_h, 0, u8_luma(c[0], c[1], c[2]));
+    });
+    u8_hist_merge(s_h, p.hist + (int64_t)n * 256);
 }
 
 // ---- the streaming pass: grid (chunks, N * T) ------------------------------------------------------------------------------
 __global__ __launch_bounds__(SF_THREADS) void sf_sslcolor_stream_kernel(SslColorParams p) {
-#pragma clang fp contract(off)
     __shared__ int s_h[256];
     const int frame = blockIdx.y;
     const int n = frame / p.T;
@@ -267,73 +218,15 @@ __global__ __launch_bounds__(SF_THREADS) void sf_sslcolor_stream_kernel(SslColor
     const SslColorRow r = sslcolor_row(row);
     const int h = row[9], w = row[10];
     const bool work = (r.flags & (SF_SSLCOLOR_JITTER | SF_SSLCOLOR_GREY)) != 0;
-    const unsigned char* base = p.src + (int64_t)frame * p.slab * 3;
-    unsigned char* obase = p.dst + (int64_t)frame * p.slab * 3;
-    if (!work && base == obase) return;                     // in place and nothing drawn
-    const int p0 = blockIdx.x * SF_RANDAUG_CHUNK;
+    if (!work && p.dst == p.src) return;                    // in place and nothing drawn
     int mean = 0;
     if (sslcolor_needs_hist(r.flags, r.order)) {            // uniform: the whole workgroup reaches the barrier
         s_h[threadIdx.x] = p.hist[(int64_t)n * 256 + threadIdx.x];
         __syncthreads();
-        int64_t sum = 0, count = 0;
-        for (int k = 0; k < 256; ++k) {
-            sum += (int64_t)k * s_h[k];
-            count += s_h[k];
-        }
-        const double m = (double)sum / (double)count;       // count > 0: h, w > 0
-        mean = (int)(m + 0.5);
+        mean = u8_hist_mean(s_h);                           // count > 0: h, w > 0
     }
-    if (p.vec) {
-        const int q = p0 + threadIdx.x * SF_RANDAUG_PIX;    // slab % 16 == 0: a group is inside the slab or outside as a whole
-        if (q >= p.slab) return;
-        uint32_t v[12], o[12];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const ra_u32x4 in = *reinterpret_cast<const ra_u32x4*>(base + (int64_t)q * 3 + 16 * k);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[4 * k + e] = in[e];
-        }
-        if (!work) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o[k] = v[k];
-        } else {
-            uint32_t y, x;
-            fd_divmod((uint32_t)q, p.fdW, y, x);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o[k] = 0;
-#pragma unroll
-            for (int e = 0; e < SF_RANDAUG_PIX; ++e) {
-                int c[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) c[k] = (v[(3 * e + k) >> 2] >> (8 * ((3 * e + k) & 3))) & 255u;
-                if ((int)y < h && (int)x < w) sslcolor_pixel<false>(c, r, mean);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) o[(3 * e + k) >> 2] |= (uint32_t)c[k] << (8 * ((3 * e + k) & 3));
-                if ((int)++x == p.Ws) { x = 0; ++y; }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            ra_u32x4 st;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) st[e] = o[4 * k + e];
-            *reinterpret_cast<ra_u32x4*>(obase + (int64_t)q * 3 + 16 * k) = st;
-        }
-        return;
-    }
-    for (int k = 0; k < SF_RANDAUG_PIX; ++k) {
-        const int q = p0 + k * SF_THREADS + threadIdx.x;
-        if (q >= p.slab) break;
-        uint32_t y, x;
-        fd_divmod((uint32_t)q, p.fdW, y, x);
-        const unsigned char* px = base + (int64_t)q * 3;
-        int c[3] = {px[0], px[1], px[2]};
-        if (work && (int)y < h && (int)x < w) sslcolor_pixel<false>(c, r, mean);
-        unsigned char* po = obase + (int64_t)q * 3;
-        po[0] = (unsigned char)c[0];
-        po[1] = (unsigned char)c[1];
-        po[2] = (unsigned char)c[2];
-    }
+    // nothing drawn into another buffer is a copy: an empty valid region
+    u8_walk<true>(p, frame, blockIdx.x, work ? h : 0, w, p.vec, [=](int (&c)[3], int, int) { sslcolor_pixel<false>(c, r, mean); });
 }
 
 // ---- the blur -------------------------------------------------------------------------------------------------------------

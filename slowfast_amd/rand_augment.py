@@ -69,8 +69,6 @@ AugRow = collections.namedtuple("AugRow", ["op", "skip", "arg"])
 # ops: int32 (N, L); skip: bool (N, L); args: float64 (N, L); filter: 0 bilinear / 1 bicubic (what the affine ops resample with)
 AugTable = collections.namedtuple("AugTable", ["ops", "skip", "args", "filter"])
 
-_scratch = {}           # (device, N, T, Hs, Ws) -> (ping-pong buffer, histograms, lookup tables)
-
 
 def _filter_id(interpolation):
     if interpolation == "random":
@@ -154,18 +152,6 @@ def _check_table(table, N):
                 raise SfError("RandAugment: row %d layer %d: SolarizeAdd adds 0 .. 255 (got %d)" % (n, l, arg))
 
 
-def _check_sizes(sizes, N, Hs, Ws):
-    if sizes is None:
-        return [(Hs, Ws)] * N
-    sizes = [(int(s[0]), int(s[1])) for s in sizes]
-    if len(sizes) != N:
-        raise SfError("RandAugment: sizes has %d entries, the batch has %d samples" % (len(sizes), N))
-    for n, (h, w) in enumerate(sizes):
-        if not (0 < h <= Hs and 0 < w <= Ws):
-            raise SfError("RandAugment: sample %d: valid size %d x %d is not inside the %d x %d buffer" % (n, h, w, Hs, Ws))
-    return sizes
-
-
 def pack_words(table, sizes):
     """AugTable + the samples' (h, w) -> the int32 words of csrc/sf_randaug.h, layer-major: row (l, n) at (l * N + n)."""
     N, L = table.ops.shape
@@ -201,15 +187,6 @@ def pack_words(table, sizes):
     return np.ascontiguousarray(words.reshape(-1))
 
 
-def _scratch_for(frames):
-    N, T, Hs, Ws, _ = frames.shape
-    key = (frames.device, N, T, Hs, Ws)
-    if key not in _scratch:
-        _scratch[key] = (torch.empty_like(frames), torch.empty((N * T, 4, 256), dtype=torch.int32, device=frames.device),
-                         torch.empty((N * T, 3, 256), dtype=torch.uint8, device=frames.device))
-    return _scratch[key]
-
-
 def rand_augment_clip(frames, table, sizes=None, out=None):
     """Applies ``table`` to the dense uint8 (N, T, Hs, Ws, 3) device buffer; ``sizes[n] = (h, w)``: the valid frame size of
     sample n (default: the whole buffer).  Returns a uint8 tensor of the same shape (``out``: the tensor to write into) and
@@ -217,18 +194,18 @@ def rand_augment_clip(frames, table, sizes=None, out=None):
     stream = spatial_sampling.check_frames(frames, "RandAugment")
     N, T, Hs, Ws, _ = frames.shape
     _check_table(table, N)
-    sizes = _check_sizes(sizes, N, Hs, Ws)
+    sizes = spatial_sampling.check_sizes(frames, sizes, "RandAugment")
+    spatial_sampling.check_out(frames, out, "RandAugment")
     if out is None:
         out = torch.empty_like(frames)
-    elif not (torch.is_tensor(out) and out.shape == frames.shape and out.dtype == torch.uint8 and out.is_contiguous()
-              and out.device == frames.device and out.data_ptr() != frames.data_ptr()):
-        raise SfError("RandAugment: out must be another dense uint8 %s tensor on the frames' device" % (tuple(frames.shape),))
     host = pack_words(table, sizes)
     L = table.ops.shape[1]
     if L == 0 or frames.numel() == 0:
         return out.copy_(frames)
     dev = torch.from_numpy(host).to(frames.device)          # every layer's rows: one host-to-device copy
-    tmp, hist, lut = _scratch_for(frames)
+    # the ping-pong buffer, the histograms (R, G, B, L) and the lookup tables of every frame
+    tmp, hist, lut = spatial_sampling.frame_scratch(frames, "RandAugment", ((N * T, 4, 256), torch.int32),
+                                                    ((N * T, 3, 256), torch.uint8))
     lib = get_lib()
     rows = host.reshape(L, N, ROW_WORDS)
     src = frames
@@ -338,7 +315,7 @@ class RandAugment:
     def __call__(self, frames, table=None, sizes=None, out=None):
         """Augments the uint8 (N, T, Hs, Ws, 3) frames; draws when no table is given."""
         spatial_sampling.check_frames(frames, "RandAugment")   # before the draw: a rejected call consumes no random numbers
-        _check_sizes(sizes, frames.shape[0], frames.shape[2], frames.shape[3])
+        spatial_sampling.check_sizes(frames, sizes, "RandAugment")
         if table is None:
             table = self.sample_batch(frames.shape[0])
         return rand_augment_clip(frames, table, sizes, out)

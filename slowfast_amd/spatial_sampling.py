@@ -76,6 +76,49 @@ def check_frames(frames, who="SpatialSampling"):
     return ops._stream(frames)
 
 
+# ---- what the uint8 passes over the frame buffer share (rand_augment, ssl_color) ----------------------------------------------
+def check_sizes(frames, sizes, who):
+    """``sizes[n] = (h, w)``: the valid frame size of sample n inside the (N, T, Hs, Ws, 3) buffer; None: the whole buffer."""
+    N, _, Hs, Ws, _ = frames.shape
+    if sizes is None:
+        return [(Hs, Ws)] * N
+    sizes = [(int(s[0]), int(s[1])) for s in sizes]
+    if len(sizes) != N:
+        raise SfError("%s: sizes has %d entries, the batch has %d samples" % (who, len(sizes), N))
+    for n, (h, w) in enumerate(sizes):
+        if not (0 < h <= Hs and 0 < w <= Ws):
+            raise SfError("%s: sample %d: valid size %d x %d is not inside the %d x %d buffer" % (who, n, h, w, Hs, Ws))
+    return sizes
+
+
+def check_out(frames, out, who, in_place=False):
+    """``out`` of a pass over ``frames``: None, another dense uint8 tensor of their shape, or -- where the pass can work
+    ``in_place`` -- the frames themselves or a tensor that does not overlap them."""
+    if out is None or (in_place and out is frames):
+        return
+    ok = (torch.is_tensor(out) and out.shape == frames.shape and out.dtype == torch.uint8 and out.is_contiguous()
+          and out.device == frames.device and (in_place or out.data_ptr() != frames.data_ptr()))
+    if not ok:
+        raise SfError("%s: out must be %s dense uint8 %s tensor on the frames' device" % (
+            who, "a" if in_place else "another", tuple(frames.shape)))
+    a, b, nbytes = frames.data_ptr(), out.data_ptr(), frames.numel()
+    if in_place and a < b + nbytes and b < a + nbytes:
+        raise SfError("%s: out must be the frames tensor itself (in place) or must not overlap it" % who)
+
+
+_scratch = {}           # (who, device, N, T, Hs, Ws) -> (a buffer like the frames, the pass's tables)
+
+
+def frame_scratch(frames, who, *tables):
+    """A second buffer like ``frames`` and one tensor per (shape, dtype) of ``tables``, uninitialised; allocated on the first
+    call for a (device, N, T, Hs, Ws) and kept: no allocation afterwards."""
+    key = (who, frames.device) + tuple(frames.shape[:4])
+    if key not in _scratch:
+        _scratch[key] = (torch.empty_like(frames),) + tuple(torch.empty(shape, dtype=dtype, device=frames.device)
+                                                            for shape, dtype in tables)
+    return _scratch[key]
+
+
 def sample_clip(frames, table, mean, std, out=None):
     """uint8 (N, T, Hs, Ws, 3) frames (every sample padded to the batch's largest frame) -> the normalised, resized, cropped and
     flipped dense fp32 (N, 3, T, S, S) clip of ``table``, channels in ``mean`` order: one launch.  ``out``: a tensor of that

@@ -64,8 +64,6 @@ SslRow = collections.namedtuple("SslRow", ["jitter", "order", "brightness", "con
 # rows: a tuple of N SslRows; gray_first: grey comes before the jitter (the non-MoCo branch)
 SslTable = collections.namedtuple("SslTable", ["rows", "gray_first"])
 
-_scratch = {}           # (device, N, T, Hs, Ws) -> (the blur's intermediate buffer, the clip histograms)
-
 
 def make_table(rows, gray_first=False):
     """An explicit SslTable from N SslRow-like tuples."""
@@ -123,18 +121,6 @@ def _check_table(table, N):
             raise SfError("SslColorJitter: row %d: the blur's sigma %r is not in [%s, %s]" % ((n, r.sigma) + BLUR_SIGMA))
 
 
-def _check_sizes(sizes, N, Hs, Ws):
-    if sizes is None:
-        return [(Hs, Ws)] * N
-    sizes = [(int(s[0]), int(s[1])) for s in sizes]
-    if len(sizes) != N:
-        raise SfError("SslColorJitter: sizes has %d entries, the batch has %d samples" % (len(sizes), N))
-    for n, (h, w) in enumerate(sizes):
-        if not (0 < h <= Hs and 0 < w <= Ws):
-            raise SfError("SslColorJitter: sample %d: valid size %d x %d is not inside the %d x %d buffer" % (n, h, w, Hs, Ws))
-    return sizes
-
-
 def pack_words(table, sizes):
     """SslTable + the samples' (h, w) -> the int32 words of csrc/sf_sslcolor.h, row n at n * ROW_WORDS."""
     N = len(table.rows)
@@ -160,34 +146,15 @@ def pack_words(table, sizes):
     return np.ascontiguousarray(words.reshape(-1))
 
 
-def _scratch_for(frames):
-    N, T, Hs, Ws, _ = frames.shape
-    key = (frames.device, N, T, Hs, Ws)
-    if key not in _scratch:
-        _scratch[key] = (torch.empty_like(frames), torch.empty((N, 256), dtype=torch.int32, device=frames.device))
-    return _scratch[key]
-
-
 def _needs_hist(row):
     return bool(row[0] & FLAG_JITTER) and any(((int(row[1]) >> (4 * k)) & 15) == CONTRAST for k in range(4))
-
-
-def _check_out(frames, out):
-    if out is None or out is frames:
-        return
-    if not (torch.is_tensor(out) and out.shape == frames.shape and out.dtype == torch.uint8 and out.is_contiguous()
-            and out.device == frames.device):
-        raise SfError("SslColorJitter: out must be a dense uint8 %s tensor on the frames' device" % (tuple(frames.shape),))
-    a, b, nbytes = frames.data_ptr(), out.data_ptr(), frames.numel()
-    if a < b + nbytes and b < a + nbytes:
-        raise SfError("SslColorJitter: out must be the frames tensor itself (in place) or must not overlap it")
 
 
 def apply_words(frames, host, out=None):
     """The launches for the packed rows ``host`` (``pack_words``; the library validates them): see ``ssl_color_clip``."""
     stream = spatial_sampling.check_frames(frames, "SslColorJitter")
     N, T, Hs, Ws, _ = frames.shape
-    _check_out(frames, out)
+    spatial_sampling.check_out(frames, out, "SslColorJitter", in_place=True)
     in_place = out is frames
     if out is None:
         out = torch.empty_like(frames)
@@ -201,7 +168,7 @@ def apply_words(frames, host, out=None):
     if frames.numel() == 0 or not np.any(flags & (FLAG_JITTER | FLAG_GREY | FLAG_BLUR)):
         return out if in_place else out.copy_(frames)
     dev = torch.from_numpy(host).to(frames.device)          # one host-to-device copy
-    tmp, hist = _scratch_for(frames)
+    tmp, hist = spatial_sampling.frame_scratch(frames, "SslColorJitter", ((N, 256), torch.int32))   # the blur's buffer, L
     lib = get_lib()
     args = (N, T, Hs, Ws, host.ctypes.data, dev.data_ptr())
     need_hist = any(_needs_hist(r) for r in rows)
@@ -223,10 +190,9 @@ def ssl_color_clip(frames, table, sizes=None, out=None):
     streaming pass, one row and one column blur pass; nothing when every row is a no-op (the result is then a copy of the
     frames, or the frames themselves in place)."""
     spatial_sampling.check_frames(frames, "SslColorJitter")
-    N, _, Hs, Ws, _ = frames.shape
-    _check_table(table, N)
-    sizes = _check_sizes(sizes, N, Hs, Ws)
-    _check_out(frames, out)
+    _check_table(table, frames.shape[0])
+    sizes = spatial_sampling.check_sizes(frames, sizes, "SslColorJitter")
+    spatial_sampling.check_out(frames, out, "SslColorJitter", in_place=True)
     return apply_words(frames, pack_words(table, sizes), out)
 
 
@@ -289,7 +255,7 @@ class SslColorJitter:
     def __call__(self, frames, table=None, sizes=None, out=None):
         """Augments the uint8 (N, T, Hs, Ws, 3) frames; draws when no table is given."""
         spatial_sampling.check_frames(frames, "SslColorJitter")    # before the draw: a rejected call consumes no random numbers
-        _check_sizes(sizes, frames.shape[0], frames.shape[2], frames.shape[3])
+        spatial_sampling.check_sizes(frames, sizes, "SslColorJitter")
         if table is None:
             table = self.sample_batch(frames.shape[0])
         return ssl_color_clip(frames, table, sizes, out)

@@ -379,7 +379,8 @@ def big_shapes():
     return [(71, 67), (80, 67), (3, 600)]
 
 
-def check_parity_big(device, which):
+def big_case(which):
+    """(sizes, frames per sample, table, padded buffer) of ``check_parity_big``."""
     Hs, Ws = big_shapes()[which]
     if which < 2:
         assert Hs * Ws > 4096 and ((Hs * Ws) % 16 == 0) == (which == 1) and Ws > 64 and Ws % 4
@@ -389,13 +390,32 @@ def check_parity_big(device, which):
         sizes = [(Hs, Ws), (Hs - 1, Ws - 85)]
     frames = case_frames(100 + which, sizes, frames_per_clip=2)
     table = sc.SslTable((_row((0, 2, 1, 3), gray=False, sigma=1.7, **FULL), _row((3, 1, 2, 0), gray=True, sigma=0.45, **FULL)), False)
-    buf = padded(frames, fill=201)
+    return sizes, frames, table, padded(frames, fill=201)
+
+
+def check_parity_big(device, which):
+    sizes, frames, table, buf = big_case(which)
+    Hs, Ws = big_shapes()[which]
     got = sa.ssl_color_clip(buf.to(device), table, sizes).cpu()
     want = restate_batch(frames, table)
     bad = [differing(got[n, :, :h, :w], want[n]) for n, (h, w) in enumerate(sizes)]
     print("%d x %d: differing bytes per sample %s" % (Hs, Ws, bad))
     assert bad == [0, 0], (Hs, Ws, bad)
     assert torch.equal(got[1, :, sizes[1][0]:], buf[1, :, sizes[1][0]:]) and torch.equal(got[1, :, :, sizes[1][1]:], buf[1, :, :, sizes[1][1]:])
+
+
+def check_in_place_big(device, which):
+    """The streaming pass in place (``out`` is the frames) across more than one chunk, on the thread-per-pixel accesses
+    (``which`` 0) and the 16-byte ones (1): a thread reads its pixels before it writes them, so the bytes are those of the
+    out-of-place call."""
+    sizes, _, table, buf = big_case(which)
+    want = sa.ssl_color_clip(buf.to(device), table, sizes).cpu()
+    dev = buf.clone().to(device)                            # on the CPU ``to`` returns the tensor itself
+    res = sa.ssl_color_clip(dev, table, sizes, out=dev)
+    assert res is dev and not torch.equal(want, buf), "the table must change something"
+    bad = differing(dev.cpu(), want)
+    print("%d x %d in place: %d bytes differ from the out-of-place result" % (big_shapes()[which] + (bad,)))
+    assert bad == 0, (which, bad)
 
 
 # ---- 4. HSV -----------------------------------------------------------------------------------------------------------

@@ -23,6 +23,11 @@ def test_restatement_parity_many_chunks(gpu, which):
     checks.check_parity_big(gpu, which)
 
 
+@pytest.mark.parametrize("which", [0, 1])
+def test_in_place_many_chunks(gpu, which):
+    checks.check_in_place_big(gpu, which)
+
+
 def test_hue_subset(gpu):
     checks.check_hue_subset(gpu)
 

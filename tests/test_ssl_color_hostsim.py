@@ -37,6 +37,11 @@ def test_restatement_parity_many_chunks(sim, which):
     checks.check_parity_big(sim, which)
 
 
+@pytest.mark.parametrize("which", [0, 1])
+def test_in_place_many_chunks(sim, which):
+    checks.check_in_place_big(sim, which)
+
+
 @pytest.mark.parametrize("direction", ["rgb_to_hsv", "hsv_to_rgb"])
 def test_hsv_restatement_against_pil_exhaustive(direction):
     checks.check_hsv_exhaustive(direction)
