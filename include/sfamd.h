@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 35
+#define SF_ABI_VERSION 36
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -141,6 +141,18 @@ int sf_conv_c_bwd(const sf_conv_desc* d, const void* dz, int32_t lddz, const voi
                   const void* bn_y, int32_t bn_ldy, float* bn_part, int32_t bn_part_rows, int32_t* bn_rows, void* d_in,
                   int32_t ld_in, float* dw, float out_scale, int zero_first, void* workspace, int64_t workspace_bytes,
                   sf_stream_t stream);
+/* The same fusion for the projection shortcut of a stage's first block (ABI 36; ResBlock.branch1 + branch1_bn, resnet_helper.py:485-499,
+ * :512-521): replaces sf_bn_bwd_apply(dz, mask_bits, y1, coef) -> dy1, sf_conv_wgrad(x, dy1) and sf_conv_dgrad(dy1, wd) of a 1x1x1
+ * unpadded, undilated convolution d of stride (1,1,1), or (1,2,2) with Hi == 2 Ho and Wi == 2 Wo, bit for bit.
+ * sf_conv_proj_bwd_plan: 1 when d takes this path (Ci % 8 == 0 <= 128, Co % 32 == 0 <= 256, in_affine == 0, mask_bits != 0), else 0;
+ * *workspace_bytes = size of `workspace`.  The test hook SF_CBWD=0 switches this path off together with sf_conv_c_bwd.
+ * sf_conv_proj_bwd: dz [Mo][lddz], mask_bits [Mo][Co/8], y1 [Mo][ldy1] the raw output of d, coef [3][Co] from sf_bn_bwd_finalize,
+ * x [Mi][d->ldx] the block input, wd the packed data-gradient operand (Mo / Mi = output / input positions).  Outputs: d_in [Mi][ld_in],
+ * EVERY row written (the input rows a stride of 2 never samples are +0), dw as sf_conv_wgrad writes it. */
+int sf_conv_proj_bwd_plan(const sf_conv_desc* d, int in_affine, int mask_bits, int64_t* workspace_bytes);
+int sf_conv_proj_bwd(const sf_conv_desc* d, const void* dz, int32_t lddz, const void* mask_bits, const void* y1, int32_t ldy1,
+                     const float* coef, const void* x, const void* wd, void* d_in, int32_t ld_in, float* dw, float out_scale,
+                     int zero_first, void* workspace, int64_t workspace_bytes, sf_stream_t stream);
 
 /* ---- BatchNorm3d -- replaces nn.BatchNorm3d built by batchnorm_helper.py:16-37 (get_norm) at every
  * *_bn call site of resnet_helper.py / stem_helper.py / video_model_builder.py:155-159, plus the

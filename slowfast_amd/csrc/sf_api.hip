@@ -1019,8 +1019,30 @@ static void cbwd_fill(CbwdPlan& w) {
         else if ((cip) == 64 && (cop) == 32) { constexpr int CIP_ = 64, COP_ = 32; __VA_ARGS__; }       \
         else if ((cip) == 64 && (cop) == 64) { constexpr int CIP_ = 64, COP_ = 64; __VA_ARGS__; }       \
         else if ((cip) == 64 && (cop) == 128) { constexpr int CIP_ = 64, COP_ = 128; __VA_ARGS__; }     \
-        else { constexpr int CIP_ = 64, COP_ = 256; __VA_ARGS__; }                                      \
+        else if ((cip) == 64 && (cop) == 256) { constexpr int CIP_ = 64, COP_ = 256; __VA_ARGS__; }     \
+        else if ((cip) == 128 && (cop) == 32) { constexpr int CIP_ = 128, COP_ = 32; __VA_ARGS__; }     \
+        else if ((cip) == 128 && (cop) == 64) { constexpr int CIP_ = 128, COP_ = 64; __VA_ARGS__; }     \
+        else if ((cip) == 128 && (cop) == 128) { constexpr int CIP_ = 128, COP_ = 128; __VA_ARGS__; }   \
+        else { constexpr int CIP_ = 128, COP_ = 256; __VA_ARGS__; }                                     \
     } while (0)
+// Who sums which of the M output rows: as the weight gradient of the three-launch path would (see above).  Returns the workgroup
+// count; *rps = rows per workgroup, or 0 for the round robin over 128-row tiles of the thin plan.
+static int cbwd_deal_rows(const sf_conv_desc* d, int64_t M, int* rps) {
+    const WgradPlan w2 = plan_conv_wgrad(d, false);
+    const int forced = test_hook("SF_CBWD_WGS", 0);
+    if (forced > 0) {
+        const int wgs = forced < SF_CBWD_MAX_WGS ? forced : SF_CBWD_MAX_WGS;
+        *rps = roundup(cdiv(M, wgs), 32);
+        return cdiv(M, *rps);
+    }
+    if (w2.path == WGRAD_ROWTAB && w2.thin && w2.splits <= SF_CBWD_MAX_WGS) {
+        *rps = 0;
+        return w2.splits;
+    }
+    const WgradPlan w1 = plan_wgrad1(d);
+    *rps = w1.chunks_per_split * 32;
+    return w1.splits;
+}
 static CbwdPlan plan_cbwd(const sf_conv_desc* d, bool in_affine, bool mask_bits) {
     CbwdPlan w;
     memset(&w, 0, sizeof(w));
@@ -1077,27 +1099,78 @@ extern "C" int sf_conv_c_bwd(const sf_conv_desc* d, const void* dz, int32_t lddz
     p.coef = coef; p.act = (const f16*)act; p.ldact = d->ldx; p.wd = (const f16*)wd; p.ldw = ldd;
     if (fuse) { p.bnb_y = (const f16*)bn_y; p.bnb_ld = bn_ldy; p.bnb_scale = bn_scale; p.bnb_shift = bn_shift; p.bnb_part = bn_part; }
     p.dx = (f16*)d_in; p.lddx = ld_in; p.ws = (float*)workspace; p.tiles128 = ntiles;
-    // who sums which rows: as the weight gradient of the three-launch path would (see above)
-    int wgs;
-    const WgradPlan w2 = plan_conv_wgrad(d, false);
-    const int forced = test_hook("SF_CBWD_WGS", 0);
-    if (forced > 0) {
-        wgs = forced < SF_CBWD_MAX_WGS ? forced : SF_CBWD_MAX_WGS;
-        p.rps = roundup(cdiv(M, wgs), 32);
-        wgs = cdiv(M, p.rps);
-    } else if (w2.path == WGRAD_ROWTAB && w2.thin && w2.splits <= SF_CBWD_MAX_WGS) {
-        wgs = w2.splits; p.rps = 0;
-    } else {
-        const WgradPlan w1 = plan_wgrad1(d);
-        wgs = w1.splits; p.rps = w1.chunks_per_split * 32;
-        REQUIRE(wgs <= SF_CBWD_MAX_WGS, "sf_conv_c_bwd: %d splits", wgs);
-    }
+    const int wgs = cbwd_deal_rows(d, M, &p.rps);
+    REQUIRE(wgs <= SF_CBWD_MAX_WGS, "sf_conv_c_bwd: %d splits", wgs);
     hipStream_t s = (hipStream_t)stream;
     SF_CBWD_FOR_SHAPE(w.cip, w.cop, hipLaunchKernelGGL((sf_cbwd_kernel<CIP_, COP_>), dim3(wgs), dim3(SF_THREADS), 0, s, p));
     if (check_launch("conv_c_bwd")) return -1;
     if (bn_rows) *bn_rows = fuse ? ntiles : 0;
     launch_wgrad_reduce(d, (const float*)workspace, wgs, w.cop, w.cip, false, dw, out_scale, zero_first, s);
     return check_launch("conv_c_bwd_reduce");
+}
+
+// The projection shortcut of a stage's first block (branch1 + branch1_bn): the same kernel with the block input in the place of
+// act_b, no inner BatchNorm, Ci up to 128 and -- at a spatial stride of 2 -- the row map of sf_cbwd.h.  Its own planner (again the
+// geometry alone; SF_CBWD=0 switches the whole family off): 1x1x1, unpadded, undilated, stride (1,1,1) or (1,2,2) over even H and W.
+// The rows are OUTPUT rows, dealt as above; the workspace is one slab per workgroup of that deal.
+static CbwdPlan plan_proj_bwd(const sf_conv_desc* d, bool in_affine, bool mask_bits) {
+    CbwdPlan w;
+    memset(&w, 0, sizeof(w));
+    if (test_hook("SF_CBWD", 1) == 0) return w;
+    if (d->kT != 1 || d->kH != 1 || d->kW != 1 || d->pT || d->pH || d->pW || d->dT != 1 || d->dH != 1 || d->dW != 1) return w;
+    const bool unit = d->sH == 1 && d->sW == 1 && d->Ho == d->Hi && d->Wo == d->Wi;
+    const bool half = d->sH == 2 && d->sW == 2 && d->Hi == 2 * d->Ho && d->Wi == 2 * d->Wo;
+    if (d->sT != 1 || d->To != d->Ti || !(unit || half)) return w;
+    if (d->Ci % 8 || d->Ci > 128 || d->Co % 32 || d->Co > 256) return w;
+    if (in_affine || !mask_bits) return w;
+    w.cip = d->Ci <= 16 ? 16 : d->Ci <= 32 ? 32 : d->Ci <= 64 ? 64 : 128;
+    w.cop = d->Co <= 32 ? 32 : d->Co <= 64 ? 64 : d->Co <= 128 ? 128 : 256;
+    int rps;
+    const int wgs = cbwd_deal_rows(d, (int64_t)d->N * d->To * d->Ho * d->Wo, &rps);
+    if (wgs > SF_CBWD_MAX_WGS) return w;
+    w.R = 128;
+    w.ws_bytes = (size_t)wgs * w.cop * w.cip * 4;
+    w.ok = true;
+    return w;
+}
+
+extern "C" int sf_conv_proj_bwd_plan(const sf_conv_desc* d, int in_affine, int mask_bits, int64_t* workspace_bytes) {
+    if (check_desc(d)) return -1;
+    const CbwdPlan w = plan_proj_bwd(d, in_affine != 0, mask_bits != 0);
+    if (workspace_bytes) *workspace_bytes = w.ok ? (int64_t)w.ws_bytes : 0;
+    return w.ok ? 1 : 0;
+}
+
+extern "C" int sf_conv_proj_bwd(const sf_conv_desc* d, const void* dz, int32_t lddz, const void* mask_bits, const void* y1,
+                                int32_t ldy1, const float* coef, const void* x, const void* wd, void* d_in, int32_t ld_in,
+                                float* dw, float out_scale, int zero_first, void* workspace, int64_t workspace_bytes,
+                                sf_stream_t stream) {
+    if (check_desc(d)) return -1;
+    REQUIRE(dz && mask_bits && y1 && coef && x && wd && d_in && dw && workspace, "sf_conv_proj_bwd: null pointer");
+    const CbwdPlan w = plan_proj_bwd(d, false, true);
+    REQUIRE(w.ok, "sf_conv_proj_bwd: this geometry keeps sf_bn_bwd_apply + sf_conv_wgrad + sf_conv_dgrad (sf_conv_proj_bwd_plan == 0)");
+    REQUIRE(lddz >= d->Co && lddz % 8 == 0 && ldy1 >= d->Co && ldy1 % 8 == 0 && ld_in >= d->Ci && ld_in % 8 == 0 &&
+            d->ldx >= d->Ci && d->ldx % 8 == 0, "sf_conv_proj_bwd: bad row pitch");
+    REQUIRE((((uintptr_t)dz | (uintptr_t)y1 | (uintptr_t)x | (uintptr_t)wd | (uintptr_t)d_in | (uintptr_t)workspace) & 15) == 0,
+            "sf_conv_proj_bwd: operands must be 16-byte aligned");
+    REQUIRE(workspace_bytes >= (int64_t)w.ws_bytes, "sf_conv_proj_bwd: workspace too small (%lld < %lld bytes)",
+            (long long)workspace_bytes, (long long)w.ws_bytes);
+    const int64_t M = (int64_t)d->N * d->To * d->Ho * d->Wo;       // output rows; d_in has d->N * d->Ti * d->Hi * d->Wi
+    int32_t ldf, ldd;
+    sf_conv_weight_ld(d, &ldf, &ldd);
+    CbwdParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = (int)M; p.Ci = d->Ci; p.Co = d->Co;
+    p.dz = (const f16*)dz; p.lddz = lddz; p.bits = (const uint8_t*)mask_bits; p.yc = (const f16*)y1; p.ldyc = ldy1;
+    p.coef = coef; p.act = (const f16*)x; p.ldact = d->ldx; p.wd = (const f16*)wd; p.ldw = ldd;
+    p.dx = (f16*)d_in; p.lddx = ld_in; p.ws = (float*)workspace; p.tiles128 = cdiv(M, 128);
+    p.str2 = d->sH == 2 ? 1 : 0; p.fdWo = make_fastdiv(d->Wo);
+    const int wgs = cbwd_deal_rows(d, M, &p.rps);
+    hipStream_t s = (hipStream_t)stream;
+    SF_CBWD_FOR_SHAPE(w.cip, w.cop, hipLaunchKernelGGL((sf_cbwd_kernel<CIP_, COP_>), dim3(wgs), dim3(SF_THREADS), 0, s, p));
+    if (check_launch("conv_proj_bwd")) return -1;
+    launch_wgrad_reduce(d, (const float*)workspace, wgs, w.cop, w.cip, false, dw, out_scale, zero_first, s);
+    return check_launch("conv_proj_bwd_reduce");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -30,8 +30,14 @@
 //     16-byte rows, and the BatchNorm-backward sums of the INNER BatchNorm are taken from the stored values (bnb_accumulate /
 //     bnb_reduce_store of sf_igemm.h): one table row per 128 rows, a thread's sums running over the 128 / R tiles in row order --
 //     the tiles and the per-thread order of the 128-row data-gradient epilogue, so the table has that epilogue's bits.
-// CIP / COP are the channel counts rounded up to {16, 32, 64} / {32, 64, 128, 256}; the real counts are runtime values (columns
+// CIP / COP are the channel counts rounded up to {16, 32, 64, 128} / {32, 64, 128, 256}; the real counts are runtime values (columns
 // beyond them are zeros in LDS and never stored).
+//
+// The projection shortcut of a stage's first block (branch1 + branch1_bn, resnet_helper.py:485-499) has the same backward with the
+// block INPUT in the place of act_b and no inner BatchNorm (sf_conv_proj_bwd): Ci up to 128 (CIP 128: the Wd tile alone is up to
+// 66 KB, one workgroup per CU at COP 256), and a spatial stride of 2 as a row map -- output row (n, t, ho, wo) reads the act row
+// (n, t, 2 ho, 2 wo), its d_in goes to that row, and the owner of the output row stores the other three input rows of the 2 x 2
+// cell as zeros: d_in is written completely, as the residue-class launches of the strided data gradient write it.
 #pragma once
 #include "sf_bn.h"
 #include "sf_common.h"
@@ -52,6 +58,8 @@ struct CbwdParams {
     float* ws;                      // [gridDim.x][COP][CIP] fp32
     int rps;                        // > 0: workgroup b owns the rows [b * rps, (b + 1) * rps) (a multiple of 32); 0: 128-row tiles b, b + G, ...
     int tiles128;                   // ceil(M / 128)
+    int str2;                       // spatial stride 2 (Hi = 2 Ho, Wi = 2 Wo): M counts OUTPUT rows, act / dx have 4 M rows
+    FastDiv fdWo;                   // (str2) output row m = q * Wo + wo  ->  input row 4 Wo q + 2 wo
 };
 
 template <int CIP, int COP>
@@ -74,7 +82,9 @@ struct CbwdCfg {
     static constexpr int LDS_BYTES = LDS_ELEMS * 2;
     // registers a thread holds across the MFMA phases: accumulators + the next tile's operands
     static constexpr int HELD = 4 * NJ * (TI + TC) + 9 * NCH + 4 * NEPI;
-    static constexpr int OCC = HELD <= 72 ? 3 : 2;                          // waves per SIMD = workgroups per CU
+    static constexpr int OCC_REGS = HELD <= 72 ? 3 : 2;
+    static constexpr int OCC_LDS = 160 * 1024 / LDS_BYTES;
+    static constexpr int OCC = OCC_LDS < OCC_REGS ? OCC_LDS : OCC_REGS;     // waves per SIMD = workgroups per CU
     static_assert(R % 64 == 0 && R % RPP == 0 && NACT >= 1 && (R * ACH) % 64 == 0, "tile shape");
     static_assert(SF_THREADS % ACH == 0 && 64 % ACH == 0, "a thread keeps one d_in column group");
 };
@@ -134,6 +144,14 @@ __global__ __launch_bounds__(SF_THREADS, (CbwdCfg<CIP, COP>::OCC)) void sf_cbwd_
         if (r1 > r0) nwalk = (((r1 + 127) >> 7) - T0) * K::NSUB;
     } else if (T0 < p.tiles128) nwalk = ((p.tiles128 - 1 - T0) / G + 1) * K::NSUB;
     auto tile_m0 = [&](int q) { return (T0 + (q / K::NSUB) * Tstep) * 128 + (q % K::NSUB) * R; };
+    // the act / d_in row of output row m
+    const int Wi = 2 * (int)p.fdWo.d;
+    auto in_row = [&](int m) -> int64_t {
+        if (!p.str2) return m;
+        uint32_t qr, wo;
+        fd_divmod((uint32_t)m, p.fdWo, qr, wo);
+        return (int64_t)qr * (2 * Wi) + 2 * wo;
+    };
 
     f16x8 dzr[K::NCH], ycr[K::NCH], ybr[K::NEPI];
     uint32_t mbr[K::NCH];
@@ -163,7 +181,7 @@ __global__ __launch_bounds__(SF_THREADS, (CbwdCfg<CIP, COP>::OCC)) void sf_cbwd_
             if (q < K::NACT) {
                 const int c = q * 64 + lane;
                 const int m = m0 + c / K::ACH, cc = c % K::ACH;
-                const f16* g = (m >= r0 && m < r1 && cc * 8 < p.Ci) ? p.act + (int64_t)m * p.ldact + cc * 8 : zline;
+                const f16* g = (m >= r0 && m < r1 && cc * 8 < p.Ci) ? p.act + in_row(m) * p.ldact + cc * 8 : zline;
                 SF_GLOBAL_LOAD_LDS16_ASM(g, ActL + q * 512);
             }
         }
@@ -277,7 +295,13 @@ __global__ __launch_bounds__(SF_THREADS, (CbwdCfg<CIP, COP>::OCC)) void sf_cbwd_
             const int row = idx / K::ACH, m = m0 + row;
             if (idx < R * K::ACH && m < p.M && ecol_ok) {
                 const f16x8 v = ld16(StL + row * CIP + ecg * 8);
-                st16(p.dx + (int64_t)m * p.lddx + ecg * 8, v);
+                f16* const o = p.dx + in_row(m) * p.lddx + ecg * 8;
+                st16(o, v);
+                if (p.str2) {                                   // the three unsampled rows of the 2 x 2 cell
+                    st16(o + p.lddx, zero8());
+                    st16(o + (int64_t)Wi * p.lddx, zero8());
+                    st16(o + (int64_t)(Wi + 1) * p.lddx, zero8());
+                }
                 if (bnb) bnb_accumulate(v, ybr[e], bsc, bsh, bsg, bsgy, false, 0u);
             }
         }

@@ -531,6 +531,25 @@ class ConvUnit:
             fuse = (y0, st0.scale, st0.shift)
         return ops.conv_c_bwd(dz, bits, y, coef, x, wd, geom, dw, bn=fuse, out_scale=1.0, zero_first=zero_first)
 
+    def fused_proj_geom(self, x):
+        """The geometry of this unit -- the projection shortcut of a block -- on the block input ``x`` when its BatchNorm backward can
+        be fused into both of its gradients (ops.conv_proj_bwd; the conditions of fused_c_geom), else None."""
+        if self.bn is None or _sync_of(self.bn) is not None or not self.conv.weight.requires_grad:
+            return None
+        geom = self.geom(x.shape)
+        return geom if ops.conv_proj_bwd_plan(geom) is not None else None
+
+    def fused_proj_backward(self, geom, x, dz, y, st, bits):
+        """bn_backward(dz, y, st, zmask=bits) followed by backward(x, None, dy, need_dx=True) without the gradient dy in memory:
+        the reduction pass and the finalize (-> coef, bn.weight.grad / bn.bias.grad), then ONE launch for conv.weight.grad and d_in."""
+        bn = self.bn
+        dgamma, dbeta, accumulate = self._bn_grad_dest()
+        coef = ops.bn_bwd_coef(dz, y, bn.weight, st.mean, st.rstd, dgamma, dbeta, zmask=bits, inv_loss_scale=1.0,
+                               accumulate=accumulate)
+        dw, zero_first = _grad_dest(self.conv.weight)
+        _, wd = self.weights(geom)
+        return ops.conv_proj_bwd(dz, bits, y, coef, x, wd, geom, dw, out_scale=1.0, zero_first=zero_first)
+
     def bn_backward(self, dz, y, st, zmask=None, relu_self=False, want_g=False, part=None):
         """BatchNorm3d backward (through ReLU) -> dy; writes bn.weight.grad / bn.bias.grad.  ``part``: partial sums already
         taken by the producer of dz (backward(..., bn_fuse=...))."""
@@ -820,7 +839,11 @@ class ResBlockFn(torch.autograd.Function):
         cgeom = units[last].fused_c_geom(act[last - 1]) if last > 0 else None
         if cgeom is None:
             dy = units[last].bn_backward(dout, raw[last], bn[last], zmask=bits, part=part_c)
-        if P is not None:
+        # the projection shortcut's BatchNorm backward fused into both gradients of branch1 (ops.conv_proj_bwd): dy1 is never written
+        pgeom = P.fused_proj_geom(x) if P is not None and need_dx else None
+        if pgeom is not None:
+            dx1 = P.fused_proj_backward(pgeom, x, dout, y1, s1, bits)
+        elif P is not None:
             dy1 = P.bn_backward(dout, y1, s1, zmask=bits)
         for i in range(last, 0, -1):
             part = None
@@ -836,7 +859,8 @@ class ResBlockFn(torch.autograd.Function):
         if prev is not None and prev["sync"]:      # the PRODUCER's BatchNorm reduces its sums across ranks: not fused
             prev = None
         if P is not None:
-            dx1 = P.backward(x, None, dy1, need_dx=need_dx)
+            if pgeom is None:
+                dx1 = P.backward(x, None, dy1, need_dx=need_dx)
             dx = units[0].backward(x, None, dy, need_dx=need_dx, resid=dx1, bn_fuse=prev)
         else:       # identity shortcut: dx = dgrad_a + dout * (out > 0), the mask applied to the residual in the epilogue
             dx = units[0].backward(x, None, dy, need_dx=need_dx, resid=dout, resid_bits=bits, bn_fuse=prev)

@@ -11,7 +11,7 @@ import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 35
+ABI_VERSION = 36
 # 16-bit storage type of activations / packed weights / MFMA operands, fixed per PROCESS: SF_ACT_DTYPE=fp16 (default) loads
 # libsfamd.so, =bf16 loads libsfamd_bf16.so -- the same sources compiled with -DSF_ACT_BF16 (bfloat16 storage,
 # v_mfma_f32_16x16x32_bf16); both are what torch.cuda.amp.autocast admits on the reference side (tools/train_net.py:101-118).
@@ -102,6 +102,9 @@ _SIGNATURES = {
     "sf_conv_c_bwd_plan": (c_int, [POINTER(ConvDesc), c_int, c_int, POINTER(c_int32), POINTER(c_int64)]),
     "sf_conv_c_bwd": (c_int, [POINTER(ConvDesc), _P, c_int32, _P, _P, c_int32, _F, _P, _P, _F, _F, _P, c_int32, _F, c_int32,
                               POINTER(c_int32), _P, c_int32, _F, c_float, c_int, _P, c_int64, _P]),
+    "sf_conv_proj_bwd_plan": (c_int, [POINTER(ConvDesc), c_int, c_int, POINTER(c_int64)]),
+    "sf_conv_proj_bwd": (c_int, [POINTER(ConvDesc), _P, c_int32, _P, _P, c_int32, _F, _P, _P, _P, c_int32, _F, c_float, c_int, _P,
+                                 c_int64, _P]),
     "sf_bn_finalize": (c_int, [_F, c_int32, c_int32, c_int32, c_float, _F, _F, _F, _F, c_float, c_float, _F, _F, _F, _F, _P]),
     "sf_bn_act": (c_int, [c_int64, c_int32, _P, c_int32, _F, _F, _P, c_int32, _F, _F, c_int, _P, c_int32, _P, _P]),
     "sf_bn_bwd_blocks": (c_int, [c_int64, c_int32]),

@@ -497,6 +497,38 @@ def conv_c_bwd(dz, bits, yc, coef, act, wd, geom, dw, bn=None, out_scale=1.0, ze
     return d_in, (part[:nrows.value] if part is not None and nrows.value > 0 else None)
 
 
+def conv_proj_bwd_plan(geom, in_affine=False, mask_bits=True):
+    """workspace_bytes when sf_conv_proj_bwd takes this geometry (the projection shortcut of a stage's first block), else None: a
+    function of the geometry alone; the test hook SF_CBWD=0 is read on every call, so nothing is cached here."""
+    ws = c_int64(0)
+    ok = get_lib().call("sf_conv_proj_bwd_plan", byref(geom.desc(geom.Ci, geom.Co)), int(bool(in_affine)), int(bool(mask_bits)),
+                        byref(ws))
+    return ws.value if ok == 1 else None
+
+
+def conv_proj_bwd(dz, bits, y1, coef, x, wd, geom, dw, out_scale=1.0, zero_first=True, out=None):
+    """BatchNorm backward of a projection shortcut fused into both gradients of its 1x1x1 convolution ``geom`` (stride 1 or (1,2,2);
+    sf_conv_proj_bwd): from dz (gradient w.r.t. the block output), its 1-bit ReLU mask ``bits``, the convolution's raw output ``y1``,
+    ``coef`` (bn_bwd_coef) and the block input ``x``: dw (+)= out_scale * dL/dw and d_in -- every row of it, the rows a stride of 2
+    never samples as zeros -- without dy ever reaching memory.  Returns d_in."""
+    ws_bytes = conv_proj_bwd_plan(geom)
+    assert ws_bytes is not None, "conv_proj_bwd: the planner rejects this geometry"
+    assert tuple(x.shape) == geom.in_shape and tuple(dz.shape) == geom.out_shape and tuple(y1.shape) == geom.out_shape
+    assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == geom.Cow * geom.Cw * geom.taps
+    M = rows(y1)
+    assert bits.dtype == torch.uint8 and bits.is_contiguous() and bits.numel() == M * (geom.Co // 8)
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and tuple(coef.shape) == (3, geom.Co)
+    d_in = cl_empty(geom.in_shape, dz.device) if out is None else out
+    assert tuple(d_in.shape) == geom.in_shape
+    ws = _workspace(dz.device, ws_bytes)
+    get_lib().call("sf_conv_proj_bwd", byref(geom.desc(cl_ld(x), geom.Co)), dz.data_ptr(), cl_ld(dz), bits.data_ptr(), y1.data_ptr(),
+                   cl_ld(y1), coef.data_ptr(), x.data_ptr(), wd.data_ptr(), d_in.data_ptr(), cl_ld(d_in), dw.data_ptr(),
+                   float(out_scale), int(zero_first), ws.data_ptr(), ws.numel(), _stream(dz),
+                   work=dict(flops=4.0 * M * geom.Co * geom.Cw,
+                             bytes=2.0 * M * geom.Co * (2 + 1 / 16) + 2.0 * M * geom.Ci + 2.0 * rows(d_in) * geom.Ci))
+    return d_in
+
+
 # ------------------------------------------------------------------------------------------------
 def _pool_args(y, kernel, stride, padding):
     N, C, T, H, W = y.shape

@@ -3,7 +3,8 @@
 Times conv fwd / dgrad / wgrad and the BN/elementwise kernels with HIP events on torch's current
 stream, prints achieved TFLOP/s and algorithmic GB/s per layer.  Usage:
     python tools/microbench.py [--batch 32] [--iters 5] [--json gpurun_out/microbench.json]
-    python tools/microbench.py --cbwd [--iters 7] [--json ...]    sf_conv_c_bwd against the three launches it replaces, HBM-cold
+    python tools/microbench.py --cbwd [--iters 7] [--json ...]    sf_conv_c_bwd and sf_conv_proj_bwd against the three launches each
+                                                                  replaces, HBM-cold
 """
 import argparse
 import json
@@ -70,6 +71,14 @@ CBWD_LAYERS = [
     ("s4.fast c 32->128", 32, 32, 14, 14, 128, 6),
     ("s5.fast c 64->256", 64, 32, 7, 7, 256, 3),
 ]
+# projection shortcuts (branch1) that take sf_conv_proj_bwd: (name, Ci, T, H, W of the INPUT, Co, spatial stride, blocks per step)
+PROJ_LAYERS = [
+    ("s2.slow branch1 80->256", 80, 8, 56, 56, 256, 1, 1),
+    ("s2.fast branch1 8->32", 8, 32, 56, 56, 32, 1, 1),
+    ("s3.fast branch1 32->64 /2", 32, 32, 56, 56, 64, 2, 1),
+    ("s4.fast branch1 64->128 /2", 64, 32, 28, 28, 128, 2, 1),
+    ("s5.fast branch1 128->256 /2", 128, 32, 14, 14, 256, 2, 1),
+]
 
 
 def time_cold(fn, iters, flush):
@@ -130,6 +139,49 @@ def cbwd_rows(batch, iters, dev, only=""):
     return rows
 
 
+def proj_rows(batch, iters, dev, only=""):
+    """The fused launch (ops.conv_proj_bwd: kernel + slab reduction) against the three it replaces (sf_bn_bwd_apply, sf_conv_wgrad,
+    sf_conv_dgrad), HBM-cold, on the production projection shortcuts; W = bytes of the block-output tensor."""
+    from slowfast_amd.lib import get_lib
+    flush = torch.zeros(160 << 20, device=dev)                   # 640 MB of fp32
+    rows = []
+    for name, Ci, T, H, W, Co, st, cnt in PROJ_LAYERS:
+        if only and not any(f in name for f in only.split("|")):
+            continue
+        geom = ops.ConvGeom((batch, Ci, T, H, W), Co, (1, 1, 1), (1, st, st))
+        if ops.conv_proj_bwd_plan(geom) is None:
+            print(f"{name:28s} the planner keeps the three launches", flush=True)
+            continue
+        x, dx = ops.cl_empty(geom.in_shape, dev), ops.cl_empty(geom.in_shape, dev)
+        dz, y1, dy = (ops.cl_empty(geom.out_shape, dev) for _ in range(3))
+        for t in (x, dz, y1):
+            t.normal_()
+        M = geom.out_rows
+        bits = torch.randint(0, 256, (M, Co // 8), dtype=torch.uint8, device=dev)
+        w = torch.randn((Co, Ci, 1, 1, 1), device=dev) * 0.05
+        _, wd = ops.prep_weights(w, geom)
+        dw = torch.empty_like(w)
+        coef = torch.randn((3, Co), device=dev) * 0.1
+        lib, s = get_lib(), torch.cuda.current_stream(dev).cuda_stream
+
+        def apply():
+            lib.call("sf_bn_bwd_apply", M, Co, dz.data_ptr(), Co, bits.data_ptr(), 0, y1.data_ptr(), Co, None, None, 0,
+                     coef.data_ptr(), dy.data_ptr(), Co, None, 0, s)
+        t_fused = time_cold(lambda: ops.conv_proj_bwd(dz, bits, y1, coef, x, wd, geom, dw, out=dx), iters, flush)
+        t_apply = time_cold(apply, iters, flush)
+        t_wgrad = time_cold(lambda: ops.conv_wgrad(x, dy, geom, dw), iters, flush)
+        t_dgrad = time_cold(lambda: ops.conv_dgrad(dy, wd, geom, out=dx), iters, flush)
+        Wb = 2.0 * M * Co
+        fused_bytes = Wb * (2 + 1 / 16) + 2.0 * M * Ci + 2.0 * dx.numel()
+        row = dict(name=name, count=cnt, W_MB=Wb / 1e6, fused_us=t_fused * 1e3, apply_us=t_apply * 1e3, wgrad_us=t_wgrad * 1e3,
+                   dgrad_us=t_dgrad * 1e3, three_us=(t_apply + t_wgrad + t_dgrad) * 1e3, fused_gbs=fused_bytes / t_fused / 1e6)
+        rows.append(row)
+        print(f"{name:28s} x{cnt} W {row['W_MB']:6.1f} MB | fused {row['fused_us']:7.1f} us {row['fused_gbs']:6.0f} GB/s | apply "
+              f"{row['apply_us']:7.1f} + wgrad {row['wgrad_us']:7.1f} + dgrad {row['dgrad_us']:7.1f} = {row['three_us']:7.1f} us",
+              flush=True)
+    return rows
+
+
 def write_markdown(path, batch, rows, tot):
     """Per-geometry table: microseconds, algorithmic GB/s (operand + result bytes crossing HBM once), TFLOP/s and the
     roofline fraction max(GB/s / 8 TB/s, TFLOP/s / 2.5 PFLOP/s) of each entry point; worst shapes by time lost."""
@@ -175,12 +227,12 @@ def main():
     ap.add_argument("--markers", action="store_true", help="launch a torch.arange kernel before the fwd / dgrad / wgrad phase of "
                     "every layer and after the last one: phase separators for tools/pmc_per_layer.py under rocprofv3 --pmc")
     ap.add_argument("--md", default="", help="write the per-geometry table (us, GB/s, TFLOP/s, roofline fraction) as markdown")
-    ap.add_argument("--cbwd", action="store_true", help="only the block-final fused backward (sf_conv_c_bwd) against the three "
-                    "launches it replaces, HBM-cold, on the production shapes")
+    ap.add_argument("--cbwd", action="store_true", help="only the fused backwards (sf_conv_c_bwd, sf_conv_proj_bwd) against the "
+                    "three launches each replaces, HBM-cold, on the production shapes")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.cbwd:
-        rows = cbwd_rows(a.batch, a.iters, dev, a.filter)
+        rows = cbwd_rows(a.batch, a.iters, dev, a.filter) + proj_rows(a.batch, a.iters, dev, a.filter)
         if a.json:
             os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
             with open(a.json, "w") as f:
