@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 36
+#define SF_ABI_VERSION 37
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -778,6 +778,27 @@ int sf_byol_sim_rows(int32_t n, int32_t V, int32_t C, const float* p, int32_t ld
                      float* loss, void* ws, int64_t ws_bytes, sf_stream_t stream);
 int sf_byol_sim_finalize(int32_t n, int32_t V, int32_t C, const float* p, int32_t ld, const float* key, float inv_T, float* df,
                          float* loss, void* ws, int64_t ws_bytes, sf_stream_t stream);
+
+/* SimCLR NT-Xent loss (ABI 37) -- slowfast/models/contrastive.py: Normalize on both crops' features and the "simclr" branch of
+ * forward (:692-754), with the backward.  fp32 in every build, plain fp32 products, no floating-point atomics, every sum has one
+ * fixed order.  sf_simclr_norm, sf_simclr_rows, sf_simclr_grad, in this order with the same arguments: a, b [n] rows of C floats
+ * lda / ldb floats apart (the RAW features of the two crops), inv_T = 1 / T.  With x = [a; b] (M = 2 n rows), q_i = x_i / |x_i|,
+ * s_ij = q_i . q_j, p(i) = (i + n) mod M, E_ij = exp((s_ij - 1) / T) for j != i (the diagonal is never formed), D_i = sum_j E_ij:
+ *   loss[0] = (1 / M) sum_i ((1 - s_i,p(i)) / T + log D_i)     (= mean_i -log(exp(s_i,p(i) / T) / sum_{j != i} exp(s_ij / T)))
+ *   g_k = sum_{j != k} E_kj (1 / D_k + 1 / D_j) q_j - 2 q_p(k),   dx_k = (1 / (M T)) (g_k - q_k (q_k . g_k)) / |x_k|
+ *   da [n][C] dense = dx_0 .. dx_{n-1} = d loss / d a,   db [n][C] dense = dx_n .. dx_{M-1} = d loss / d b
+ *   q_out [n][C] dense, or null = q_0 .. q_{n-1}, the normalised rows of a (written by sf_simclr_norm)
+ * No epsilon: a zero row makes the loss and EVERY element of da and db NaN (it enters every D_j), as in the reference.  ws is
+ * sf_simclr_workspace(n, C) bytes, 16-byte aligned (q, |x|, D, the row terms and the M x M matrix E, from call to call).
+ * Accepted: 1 <= n <= 1024, 1 <= C <= 1024, lda, ldb >= C; anything else returns -1 (the workspace query too) before anything is
+ * written. */
+int64_t sf_simclr_workspace(int32_t n, int32_t C);
+int sf_simclr_norm(int32_t n, int32_t C, const float* a, int32_t lda, const float* b, int32_t ldb, float inv_T, float* da, float* db,
+                   float* loss, float* q_out, void* ws, int64_t ws_bytes, sf_stream_t stream);
+int sf_simclr_rows(int32_t n, int32_t C, const float* a, int32_t lda, const float* b, int32_t ldb, float inv_T, float* da, float* db,
+                   float* loss, float* q_out, void* ws, int64_t ws_bytes, sf_stream_t stream);
+int sf_simclr_grad(int32_t n, int32_t C, const float* a, int32_t lda, const float* b, int32_t ldb, float inv_T, float* da, float* db,
+                   float* loss, float* q_out, void* ws, int64_t ws_bytes, sf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -27,5 +27,6 @@ from .ssl_color import (SslColorJitter, SslRow, SslTable, construct_ssl_color_ji
                         ssl_color_clip)  # (SSL colour jitter / grey / blur of the decoded uint8 frames on the device)
 from .losses import get_loss_func  # noqa: F401,E402
 from . import contrastive  # noqa: F401,E402  (registers ContrastiveModel: MoCo pre-training)
-from .contrastive import (ByolSimFn, ContrastiveModel, MoCoNceFn, byol_sim, contrastive_forward,  # noqa: F401,E402
-                          contrastive_parameter_surgery, ema_update, enqueue, l2norm_rows, moco_nce)  # (MoCo / BYOL step glue)
+from .contrastive import (ByolSimFn, ContrastiveModel, MoCoNceFn, SimclrNtXentFn, byol_sim, contrastive_forward,  # noqa: F401,E402
+                          contrastive_parameter_surgery, ema_update, enqueue, l2norm_rows, moco_nce,
+                          simclr_ntxent)  # (MoCo / BYOL / SimCLR step glue)

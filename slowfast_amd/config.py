@@ -116,7 +116,7 @@ _DEFAULTS = {
     # the arithmetic is the pytorch backend's)
     "AVA": {"BGR": False, "TRAIN_USE_COLOR_AUGMENTATION": False, "TRAIN_PCA_JITTER_ONLY": True, "TEST_FORCE_FLIP": False},
     "MULTIGRID": {"SHORT_CYCLE": False, "LONG_CYCLE": False},
-    # slowfast/config/defaults.py:21-90 (contrastive.ContrastiveModel; TYPE "moco" and "byol" are the ones that run here)
+    # slowfast/config/defaults.py:21-90 (contrastive.ContrastiveModel; TYPE "moco", "byol", "simclr" are the ones that run here)
     "CONTRASTIVE": {"T": 0.07, "DIM": 128, "LENGTH": 239975, "QUEUE_LEN": 65536, "MOMENTUM": 0.5, "MOMENTUM_ANNEALING": False,
                     "TYPE": "mem", "INTERP_MEMORY": False, "MEM_TYPE": "1d", "NUM_CLASSES_DOWNSTREAM": 400,
                     "NUM_MLP_LAYERS": 1, "MLP_DIM": 2048, "BN_MLP": False, "BN_SYNC_MLP": False, "LOCAL_SHUFFLE_BN": True,
@@ -363,6 +363,30 @@ PRESETS["BYOL_SlowR50_8x8"]["BN"] = {"USE_PRECISE_STATS": False, "NUM_BATCHES_PR
 PRESETS["BYOL_SlowR50_8x8"]["SOLVER"] = {"BASE_LR": 0.6, "LARS_ON": True, "LR_POLICY": "cosine", "MAX_EPOCH": 200,
                                           "MOMENTUM": 0.9, "WEIGHT_DECAY": 1e-6, "WARMUP_EPOCHS": 35.0,
                                           "WARMUP_START_LR": 0.001, "OPTIMIZING_METHOD": "sgd"}
+
+# configs/contrastive_ssl/SimCLR_SlowR50_8x8.yaml (SimCLR pre-training of Slow-R50: 4 temporal crops, the NT-Xent loss over each
+# pair of adjacent crops; LARS.  The yaml sets SOLVER.BASE_LR twice (0.6, then 1.2) and the loader keeps the last.  NUM_GPUS and
+# BN.NUM_SYNC_DEVICES stay 1 here (the yaml has 8 and 8): statistics shared between devices and the cross-rank gather of the
+# features are not built, and with one device the "sync_batchnorm" layers and BN_SYNC_MLP come to per-device BatchNorm, as they
+# do in the reference)
+PRESETS["SimCLR_SlowR50_8x8"] = copy.deepcopy(PRESETS["SLOW_8x8_R50"])
+PRESETS["SimCLR_SlowR50_8x8"]["TASK"] = "ssl"
+PRESETS["SimCLR_SlowR50_8x8"]["NUM_GPUS"] = 1
+PRESETS["SimCLR_SlowR50_8x8"]["RESNET"]["ZERO_INIT_FINAL_BN"] = False   # the yaml leaves the default
+PRESETS["SimCLR_SlowR50_8x8"]["MODEL"] = {"NUM_CLASSES": 128, "ARCH": "slow", "MODEL_NAME": "ContrastiveModel",
+                                           "LOSS_FUNC": "contrastive_loss", "DROPOUT_RATE": 0.0, "HEAD_ACT": "none"}
+PRESETS["SimCLR_SlowR50_8x8"]["CONTRASTIVE"] = {"TYPE": "simclr", "T": 0.1, "DIM": 128, "NUM_CLASSES_DOWNSTREAM": 400,
+                                                 "NUM_MLP_LAYERS": 3, "BN_SYNC_MLP": True, "SIMCLR_DIST_ON": True,
+                                                 "SEQUENTIAL": True}
+PRESETS["SimCLR_SlowR50_8x8"]["DATA"].update({
+    "TRAIN_CROP_NUM_TEMPORAL": 4, "TRAIN_CROP_NUM_SPATIAL": 1, "TRAIN_JITTER_SCALES": [224, 224],
+    "TRAIN_JITTER_SCALES_RELATIVE": [0.2, 0.766], "TRAIN_JITTER_ASPECT_RELATIVE": [0.75, 1.3333], "SSL_MOCOV2_AUG": True,
+    "COLOR_RND_GRAYSCALE": 0.2, "SSL_COLOR_JITTER": True, "SSL_COLOR_HUE": 0.15, "SSL_COLOR_BRI_CON_SAT": [0.6, 0.6, 0.6]})
+PRESETS["SimCLR_SlowR50_8x8"]["BN"] = {"USE_PRECISE_STATS": False, "NUM_BATCHES_PRECISE": 200, "WEIGHT_DECAY": 0.0,
+                                        "NUM_SYNC_DEVICES": 1, "NORM_TYPE": "sync_batchnorm"}
+PRESETS["SimCLR_SlowR50_8x8"]["SOLVER"] = {"BASE_LR": 1.2, "LARS_ON": True, "LR_POLICY": "cosine", "MAX_EPOCH": 200,
+                                            "MOMENTUM": 0.9, "WEIGHT_DECAY": 1e-6, "WARMUP_EPOCHS": 35.0,
+                                            "WARMUP_START_LR": 0.001, "OPTIMIZING_METHOD": "sgd"}
 
 # configs/Kinetics/C2D_NLN_8x8_R50.yaml, configs/Kinetics/SLOWFAST_NLN_8x8_R50.yaml
 PRESETS["C2D_NLN_8x8_R50"] = copy.deepcopy(PRESETS["C2D_8x8_R50"])

@@ -1,5 +1,5 @@
-"""MoCo and BYOL pre-training (slowfast/models/contrastive.py, tools/train_net.py:118-172): ``ContrastiveModel`` with
-``CONTRASTIVE.TYPE == "moco"`` or ``"byol"`` on the engine's backbones, on one device, and the step glue the reference runs as
+"""MoCo, BYOL and SimCLR pre-training (slowfast/models/contrastive.py, tools/train_net.py:118-172): ``ContrastiveModel`` with
+``CONTRASTIVE.TYPE == "moco"``, ``"byol"`` or ``"simclr"`` on the engine's backbones, on one device, and the step glue the reference runs as
 torch ops on the device.
 
 Per iteration the reference makes three passes per parameter tensor for the momentum update, four small passes per feature matrix
@@ -26,6 +26,15 @@ encoder, the annealing and ``l2norm_rows`` for the keys.  Its loss is, per key v
 * ``byol_sim``     two launches: the loss of one query against all its key views and d(loss)/d(p) for the RAW predictor output.
   ``ByolSimFn.backward`` is ``grad_out * df``.
 
+SimCLR (``TYPE == "simclr"``: no momentum encoder, no queue) runs two query forwards per pair of adjacent crops.  Its loss is
+``cat``, ``mm``, ``exp``, an off-diagonal mask, ``masked_select`` (a data-dependent shape: a host synchronisation that cannot be
+captured), ``sum``, the positives, ``div``, ``log``, ``mean`` and autograd back through all of them.  Here (csrc/sf_simclr.h,
+fp32, no floating-point atomics):
+
+* ``simclr_ntxent`` three launches: the loss over the 2 n rows of both crops and d(loss)/d(a), d(loss)/d(b) for the RAW head
+  outputs; ``Normalize(a)`` for the kNN memory comes out of the first launch.  ``SimclrNtXentFn.backward`` scales the two
+  stored gradients by ``grad_out``.
+
 The dummy logits the reference builds twice per step (9999 in column 0) are built once per (rows, QUEUE_LEN, device).
 """
 import math
@@ -41,7 +50,7 @@ from .registry import MODEL_REGISTRY
 from .video_models import ResNet, SlowFast
 
 _MODEL_TYPES = {"slowfast": SlowFast, "slow": ResNet, "c2d": ResNet, "i3d": ResNet, "slow_c2d": ResNet}
-_UNSUPPORTED_TYPES = ("mem", "self", "swav", "simclr")
+_UNSUPPORTED_TYPES = ("mem", "self", "swav")
 
 
 def _dense_f32(t, what, dim=2):
@@ -186,6 +195,72 @@ def byol_sim(p, keys, T):
     return ByolSimFn.apply(p, keys.detach(), T)
 
 
+_simclr_workspaces = {}
+
+
+def _simclr_workspace(device, n, C):
+    """q, the norms, D, the row terms and the M x M matrix E of ``simclr_ntxent``, allocated once per shape.  Scratch only: what
+    a call returns (loss, da, db, q) lives in tensors of its own, so a later call of the same shape invalidates nothing."""
+    key = (device, n, C)
+    ws = _simclr_workspaces.get(key)
+    if ws is None:
+        nbytes = get_lib().call("sf_simclr_workspace", n, C)
+        ws = _simclr_workspaces[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def _pitched_f32(t, what):
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+        raise SfError("%s must be a float32 (n, C) matrix with unit column stride (got %s)" % (
+            what, "%s %s" % (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+    return t
+
+
+class SimclrNtXentFn(torch.autograd.Function):
+    """(loss, q) = f(raw features a (n, C), raw features b (n, C), T): the NT-Xent loss of the simclr branch over the 2 n rows
+    of [a; b], differentiable w.r.t. a and b; q = Normalize(a) (not differentiable: the kNN memory's input) or None.  The rows
+    of a and b may be pitched (``stride(0) >= C``, each its own).  Three launches (csrc/sf_simclr.h); both gradients are
+    computed here and kept for the backward, which scales them."""
+
+    @staticmethod
+    def forward(ctx, a, b, T, want_q):
+        _pitched_f32(a, "simclr_ntxent: a")
+        _pitched_f32(b, "simclr_ntxent: b")
+        stream = ops._stream(a)
+        n, C = a.shape
+        if tuple(b.shape) != (n, C) or b.device != a.device:
+            raise SfError("simclr_ntxent: b %s on %s does not match a %s on %s" % (tuple(b.shape), b.device, tuple(a.shape), a.device))
+        lib = get_lib()
+        ws = _simclr_workspace(a.device, n, C)          # raises for a shape the kernels do not take, before anything is allocated
+        da = torch.empty((n, C), dtype=torch.float32, device=a.device)
+        db = torch.empty((n, C), dtype=torch.float32, device=a.device)
+        loss = torch.empty((1,), dtype=torch.float32, device=a.device)
+        q = torch.empty((n, C), dtype=torch.float32, device=a.device) if want_q else None
+        M = 2 * n
+        args = (n, C, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), 1.0 / float(T), da.data_ptr(), db.data_ptr(),
+                loss.data_ptr(), ops._ptr(q), ws.data_ptr(), ws.numel() * 4, stream)
+        lib.call("sf_simclr_norm", *args, work=dict(bytes=8.0 * M * C))
+        lib.call("sf_simclr_rows", *args, work=dict(bytes=4.0 * (M * C + M * M), flops=2.0 * M * M * C))
+        lib.call("sf_simclr_grad", *args, work=dict(bytes=4.0 * (2 * M * C + M * M), flops=2.0 * M * M * C))
+        ctx.save_for_backward(da, db)
+        if want_q:
+            ctx.mark_non_differentiable(q)
+        return loss.view(()), q
+
+    @staticmethod
+    def backward(ctx, dloss, _dq):
+        da, db = ctx.saved_tensors
+        return dloss * da, dloss * db, None, None
+
+
+def simclr_ntxent(a, b, T, return_q=False):
+    """The loss of the simclr branch of ``ContrastiveModel.forward`` after the two backbone calls: ``a`` and ``b`` are the RAW
+    head outputs of ``clips[0]`` and ``clips[1]`` (both normalisations and their backward are inside).  Returns the loss, or
+    (loss, Normalize(a)) with ``return_q``."""
+    loss, q = SimclrNtXentFn.apply(a, b, T, bool(return_q))
+    return (loss, q) if return_q else loss
+
+
 _err_words = {}
 
 
@@ -291,8 +366,8 @@ class Memory(nn.Module):
 def _check_cfg(cfg):
     c = cfg.CONTRASTIVE
     if c.TYPE in _UNSUPPORTED_TYPES:
-        raise NotImplementedError("CONTRASTIVE.TYPE %r: only \"moco\" and \"byol\" run on this engine" % (c.TYPE,))
-    if c.TYPE not in ("moco", "byol"):
+        raise NotImplementedError("CONTRASTIVE.TYPE %r: only \"moco\", \"byol\" and \"simclr\" run on this engine" % (c.TYPE,))
+    if c.TYPE not in ("moco", "byol", "simclr"):
         raise NotImplementedError("CONTRASTIVE.TYPE %r" % (c.TYPE,))
     if c.TYPE == "byol":
         depths = list(c.PREDICTOR_DEPTHS)
@@ -303,6 +378,18 @@ def _check_cfg(cfg):
         if c.BN_SYNC_MLP and (cfg.BN.NUM_SYNC_DEVICES != 1 or cfg.BN.GLOBAL_SYNC):
             raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP with BN.NUM_SYNC_DEVICES %d, BN.GLOBAL_SYNC %s: the MLP heads' "
                                       "BatchNorm is per device" % (cfg.BN.NUM_SYNC_DEVICES, bool(cfg.BN.GLOBAL_SYNC)))
+    elif c.TYPE == "simclr":
+        if list(c.PREDICTOR_DEPTHS):
+            raise NotImplementedError("CONTRASTIVE.TYPE \"simclr\" with CONTRASTIVE.PREDICTOR_DEPTHS %r: predictor heads belong to "
+                                      "BYOL" % (list(c.PREDICTOR_DEPTHS),))
+        if c.MOCO_MULTI_VIEW_QUEUE:         # a MoCo key: SimCLR has no queue, a recipe that sets it is a mistake
+            raise NotImplementedError("CONTRASTIVE.TYPE \"simclr\" with CONTRASTIVE.MOCO_MULTI_VIEW_QUEUE: SimCLR has no queue")
+        if c.BN_SYNC_MLP and (cfg.BN.NUM_SYNC_DEVICES != 1 or cfg.BN.GLOBAL_SYNC):
+            raise NotImplementedError("CONTRASTIVE.BN_SYNC_MLP with BN.NUM_SYNC_DEVICES %d, BN.GLOBAL_SYNC %s: the MLP heads' "
+                                      "BatchNorm is per device" % (cfg.BN.NUM_SYNC_DEVICES, bool(cfg.BN.GLOBAL_SYNC)))
+        if cfg.NUM_GPUS * cfg.NUM_SHARDS > 1:
+            raise NotImplementedError("NUM_GPUS * NUM_SHARDS > 1: the cross-rank gather of the features (AllGatherWithGradient) "
+                                      "is not built")
     else:
         if list(c.PREDICTOR_DEPTHS):
             raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS: predictor heads belong to BYOL")
@@ -319,7 +406,11 @@ class ContrastiveModel(nn.Module):
     """The reference's constructor, ``forward(clips, index, time, epoch_exact, keys)`` and state_dict (``backbone.*``,
     ``backbone_hist.*``, ``ptr``, ``queue_x``, ``iter``, ``knn_mem.memory``) for ``CONTRASTIVE.TYPE == "moco"`` and ``"byol"``
     (the reference registers the queue buffers for byol too; with predictors the backbones' heads carry
-    ``head.predictors.0.projection.*``)."""
+    ``head.predictors.0.projection.*``).  ``"simclr"`` has no momentum encoder, queue or counters, as in the reference
+    (contrastive.py:117-119): its state_dict is ``backbone.*`` plus ``knn_mem.memory`` under ``KNN_ON``, ``bind_flat`` binds
+    nothing, and ``_update_history`` / ``set_momentum`` are never reached.  The reference's ``pos_mask`` / ``neg_mask``
+    precompute feeds only a dead branch (``distributed_loss = False``) and is not built; ``CONTRASTIVE.SIMCLR_DIST_ON`` is read
+    and ignored."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -342,15 +433,17 @@ class ContrastiveModel(nn.Module):
         self.num_crops = cfg.DATA.TRAIN_CROP_NUM_TEMPORAL * cfg.DATA.TRAIN_CROP_NUM_SPATIAL
         self.nce_loss_fun = get_loss_func("contrastive_loss")(reduction="mean")
         assert cfg.MODEL.LOSS_FUNC == "contrastive_loss"
-        self.backbone_hist = _MODEL_TYPES[cfg.MODEL.ARCH](cfg)
-        for p in self.backbone_hist.parameters():
-            p.requires_grad = False
-        self.register_buffer("ptr", torch.tensor([0]))
-        stdv = 1.0 / math.sqrt(self.dim / 3)
-        self.register_buffer("queue_x", torch.rand(self.k, self.dim).mul_(2 * stdv).add_(-stdv))
-        self.register_buffer("iter", torch.zeros([1], dtype=torch.long))
-        self._batch_shuffle_on = not (("sync" in cfg.BN.NORM_TYPE and cfg.BN.NUM_SYNC_DEVICES == cfg.NUM_GPUS)
-                                      or self.type == "byol")
+        if self.type != "simclr":           # contrastive.py:117-119: simclr has no momentum encoder, queue or counters
+            self.backbone_hist = _MODEL_TYPES[cfg.MODEL.ARCH](cfg)
+            for p in self.backbone_hist.parameters():
+                p.requires_grad = False
+            self.register_buffer("ptr", torch.tensor([0]))
+            stdv = 1.0 / math.sqrt(self.dim / 3)
+            self.register_buffer("queue_x", torch.rand(self.k, self.dim).mul_(2 * stdv).add_(-stdv))
+            self.register_buffer("iter", torch.zeros([1], dtype=torch.long))
+            self._batch_shuffle_on = not (("sync" in cfg.BN.NORM_TYPE and cfg.BN.NUM_SYNC_DEVICES == cfg.NUM_GPUS)
+                                          or self.type == "byol")
+        self.simclr_dist_on = cfg.CONTRASTIVE.SIMCLR_DIST_ON    # read and ignored: it only feeds the reference's dead branch
         if self.knn_on:
             self.knn_mem = Memory(self.length, 1, self.dim, cfg)
         # device-side step state that is no part of a checkpoint: the two momentum words and the enqueue's error word
@@ -364,7 +457,8 @@ class ContrastiveModel(nn.Module):
     # ---- checkpoint surface ---------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, *args, **kwargs):
         out = super().load_state_dict(state_dict, *args, **kwargs)
-        self._iter_host = int(self.iter.item())
+        if self.type != "simclr":
+            self._iter_host = int(self.iter.item())
         engine.PARAM_EPOCH += 1
         return out
 
@@ -388,6 +482,8 @@ class ContrastiveModel(nn.Module):
     def bind_flat(self, optimizer):
         """After ``construct_optimizer``: ``backbone_hist``'s parameters become views of one flat buffer laid out like
         ``optimizer.flat_param`` (matched by name), so that ``_update_history`` is one launch."""
+        if self.type == "simclr":           # no momentum encoder: nothing to bind (the training loop reads the same)
+            return self
         names = {id(p): n for n, p in self.backbone.named_parameters()}
         hist = dict(self.backbone_hist.named_parameters())
         flat = optimizer.flat_param
@@ -542,7 +638,7 @@ class ContrastiveModel(nn.Module):
         labels = np.zeros((self.num_imgs,), dtype=np.int32)
         for i in range(self.num_imgs):
             labels[i] = train_loader.dataset._labels[i]
-        self.train_labels = torch.LongTensor(labels).to(self.queue_x.device)
+        self.train_labels = torch.LongTensor(labels).to(self._err.device)
         if self.length != self.num_imgs:
             self.knn_mem.resize(self.num_imgs, 1, self.dim)
 
@@ -558,6 +654,8 @@ class ContrastiveModel(nn.Module):
             self.momentum_anneal_cosine(epoch_exact)
         if self.type == "byol":
             return self._forward_byol(clips, index, keys)
+        if self.type == "simclr":
+            return self._forward_simclr(clips, index)
         if isinstance(clips[0], list):
             clip_q, clips_k = clips[0], list(clips[1:])
         else:
@@ -583,6 +681,27 @@ class ContrastiveModel(nn.Module):
             self.knn_mem_update(l2norm_rows(feat_q.detach()), index)
         return logits, loss
 
+    def _forward_simclr(self, clips, index):
+        """The simclr branch (contrastive.py:692-754).  ``index is None`` returns the NORMALISED rows, as the reference does
+        here (its moco and byol branches return the raw features), detached.  Training runs the backbone on ``clips[0]`` and on
+        ``clips[1]`` in two separate calls, as there: BatchNorm statistics move twice.  Returns (dummy logits, loss); the dummy
+        logits are shared between calls (``dummy_logits``)."""
+        many = isinstance(clips[0], list)
+        feat_q = self.backbone(clips[0] if many else clips)
+        if isinstance(feat_q, list):
+            raise NotImplementedError("CONTRASTIVE.PREDICTOR_DEPTHS")
+        if index is None:
+            return l2norm_rows(feat_q.detach().float().contiguous())      # detached: a feature-extraction call
+        if not self.training:
+            return self.eval_knn(l2norm_rows(feat_q.detach().float().contiguous()))
+        assert many and len(clips) >= 2, "training takes a list of two clips"
+        feat_q2 = self.backbone(clips[1])
+        if self.knn_on:
+            loss, q = simclr_ntxent(feat_q.float(), feat_q2.float(), self.T, return_q=True)
+            self.knn_mem_update(q, index)          # the kernel's own Normalize(clips[0]): no second normalisation launch
+        else:
+            loss = simclr_ntxent(feat_q.float(), feat_q2.float(), self.T)
+        return dummy_logits(len(index), self.k, feat_q.device), loss
 
     def _forward_byol(self, clips, index, keys):
         """The byol branch (contrastive.py:485-568).  Returns (dummy logits, loss); the dummy logits are a tensor shared between
@@ -649,11 +768,21 @@ def contrastive_forward(model, cfg, inputs, index, time, epoch_exact, scaler=Non
     if cfg.CONTRASTIVE.SEQUENTIAL:
         perform_backward = False
         mdl = getattr(model, "module", model)
-        keys = mdl.compute_key_feat(inputs, compute_predictor_keys=False, batched_inference=len(inputs) < 2)
+        simclr = cfg.CONTRASTIVE.TYPE == "simclr"
+        if simclr:                              # no key encoder: pair k is crops (k, k + 1), the last crop opens no pair
+            keys = [None] * len(inputs)
+        else:
+            keys = mdl.compute_key_feat(inputs, compute_predictor_keys=False, batched_inference=len(inputs) < 2)
         for k, vid in enumerate(inputs):
             other_keys = keys[:k] + keys[k + 1:]
             time_cur = None if time is None else torch.cat([time[:, k:k + 1, :], time[:, :k, :], time[:, k + 1:, :]], 1)
-            lgt_k, loss_k = model([vid], index, time_cur, epoch_exact, keys=other_keys)
+            vids = [vid]
+            if simclr:
+                if k < len(inputs) - 1:
+                    vids = inputs[k:k + 2]
+                else:
+                    break
+            lgt_k, loss_k = model(vids, index, time_cur, epoch_exact, keys=other_keys)
             scaled = loss_k if scaler is None else (scaler.scale(loss_k) if hasattr(scaler, "scale") else scaler(loss_k))
             scaled.backward()
             if k == 0:

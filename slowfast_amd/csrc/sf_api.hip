@@ -27,6 +27,7 @@
 #include "sf_pixel.h"
 #include "sf_moco.h"
 #include "sf_byol.h"
+#include "sf_simclr.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -3822,4 +3823,60 @@ extern "C" int sf_byol_sim_finalize(int32_t n, int32_t V, int32_t C, const float
     if (byol_fill("sf_byol_sim_finalize", p, n, V, C, x, ld, key, inv_T, df, loss, ws, ws_bytes)) return -1;
     hipLaunchKernelGGL(sf_byol_sim_finalize_kernel, dim3(1), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
     return check_launch("byol_sim_finalize");
+}
+
+// ================================================================================================
+// SimCLR NT-Xent loss (sf_simclr.h; slowfast/models/contrastive.py: Normalize and the simclr branch of forward).
+static int simclr_check(const char* who, int32_t n, int32_t C) {
+    REQUIRE(n >= 1 && n <= SF_SIMCLR_NMAX, "%s: n = %d: the rows per crop must be 1 .. %d", who, n, SF_SIMCLR_NMAX);
+    REQUIRE(C >= 1 && C <= SF_SIMCLR_CMAX, "%s: C = %d: the feature dimension must be 1 .. %d", who, C, SF_SIMCLR_CMAX);
+    return 0;
+}
+static int64_t simclr_pad4(int64_t x) { return (x + 3) / 4 * 4; }
+extern "C" int64_t sf_simclr_workspace(int32_t n, int32_t C) {
+    if (simclr_check("sf_simclr_workspace", n, C)) return -1;
+    const int64_t M = 2 * (int64_t)n;
+    return 4 * (simclr_pad4(M * C) + 3 * simclr_pad4(M) + M * M);       // q, |x|, D, the row terms, E
+}
+static int simclr_fill(const char* who, SimclrParams& p, int32_t n, int32_t C, const float* a, int32_t lda, const float* b,
+                       int32_t ldb, float inv_T, float* da, float* db, float* loss, float* q_out, void* ws, int64_t ws_bytes) {
+    if (simclr_check(who, n, C)) return -1;
+    REQUIRE(a && b && da && db && loss && ws, "%s: null pointer", who);
+    REQUIRE(lda >= C && ldb >= C, "%s: row pitches %d, %d below C = %d", who, lda, ldb, C);
+    REQUIRE((uintptr_t)ws % 16 == 0, "%s: the workspace must be 16-byte aligned", who);
+    REQUIRE(ws_bytes >= sf_simclr_workspace(n, C), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
+            (long long)sf_simclr_workspace(n, C));
+    const int64_t M = 2 * (int64_t)n;
+    p.a = a; p.b = b; p.da = da; p.db = db; p.loss = loss; p.q_out = q_out;
+    p.q = (float*)ws;
+    p.nrm = p.q + simclr_pad4(M * C);
+    p.D = p.nrm + simclr_pad4(M);
+    p.term = p.D + simclr_pad4(M);
+    p.E = p.term + simclr_pad4(M);
+    p.n = n; p.M = (int)M; p.C = C; p.lda = lda; p.ldb = ldb;
+    p.cw = C <= 64 ? 64 : (C <= 128 ? 128 : SF_THREADS);
+    p.ktiles = cdiv((int)M, SF_SIMCLR_RK * (SF_THREADS / p.cw));
+    p.invT = inv_T;
+    p.coef = (float)((double)inv_T / (double)M);
+    return 0;
+}
+#define SF_SIMCLR_ARGS int32_t n, int32_t C, const float* a, int32_t lda, const float* b, int32_t ldb, float inv_T, float* da, \
+                       float* db, float* loss, float* q_out, void* ws, int64_t ws_bytes, sf_stream_t stream
+#define SF_SIMCLR_FILL(who) \
+    SimclrParams p;         \
+    if (simclr_fill(who, p, n, C, a, lda, b, ldb, inv_T, da, db, loss, q_out, ws, ws_bytes)) return -1
+extern "C" int sf_simclr_norm(SF_SIMCLR_ARGS) {
+    SF_SIMCLR_FILL("sf_simclr_norm");
+    hipLaunchKernelGGL(sf_simclr_norm_kernel, dim3(cdiv(p.M, SF_THREADS / 64)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("simclr_norm");
+}
+extern "C" int sf_simclr_rows(SF_SIMCLR_ARGS) {
+    SF_SIMCLR_FILL("sf_simclr_rows");
+    hipLaunchKernelGGL(sf_simclr_rows_kernel, dim3(cdiv(p.M, SF_SIMCLR_TI)), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("simclr_rows");
+}
+extern "C" int sf_simclr_grad(SF_SIMCLR_ARGS) {
+    SF_SIMCLR_FILL("sf_simclr_grad");
+    hipLaunchKernelGGL(sf_simclr_grad_kernel, dim3(p.ktiles + 1), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("simclr_grad");
 }

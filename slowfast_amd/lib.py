@@ -11,7 +11,7 @@ import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 36
+ABI_VERSION = 37
 # 16-bit storage type of activations / packed weights / MFMA operands, fixed per PROCESS: SF_ACT_DTYPE=fp16 (default) loads
 # libsfamd.so, =bf16 loads libsfamd_bf16.so -- the same sources compiled with -DSF_ACT_BF16 (bfloat16 storage,
 # v_mfma_f32_16x16x32_bf16); both are what torch.cuda.amp.autocast admits on the reference side (tools/train_net.py:101-118).
@@ -241,6 +241,10 @@ _SIGNATURES = {
     "sf_byol_sim_workspace": (c_int64, [c_int32, c_int32, c_int32]),
     "sf_byol_sim_rows": (c_int, [c_int32, c_int32, c_int32, _F, c_int32, _F, c_float, _F, _F, _P, c_int64, _P]),
     "sf_byol_sim_finalize": (c_int, [c_int32, c_int32, c_int32, _F, c_int32, _F, c_float, _F, _F, _P, c_int64, _P]),
+    "sf_simclr_workspace": (c_int64, [c_int32, c_int32]),
+    "sf_simclr_norm": (c_int, [c_int32, c_int32, _F, c_int32, _F, c_int32, c_float, _F, _F, _F, _F, _P, c_int64, _P]),
+    "sf_simclr_rows": (c_int, [c_int32, c_int32, _F, c_int32, _F, c_int32, c_float, _F, _F, _F, _F, _P, c_int64, _P]),
+    "sf_simclr_grad": (c_int, [c_int32, c_int32, _F, c_int32, _F, c_int32, c_float, _F, _F, _F, _F, _P, c_int64, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
