@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 37
+#define SF_ABI_VERSION 38
 typedef void* sf_stream_t;
 
 /* Geometry of one nn.Conv3d (groups == 1).  Ci is the channel count of the activation buffer
@@ -122,6 +122,29 @@ int sf_conv_wgrad_rowtab(const sf_conv_desc* d, void* tab, sf_stream_t stream);
 int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* in_scale, const float* in_shift, int in_relu,
                   const void* dy, float* dw, float out_scale, int zero_first, void* workspace, int64_t workspace_bytes,
                   const void* rowtab, sf_stream_t stream);
+/* ---- Grouped (1,3,3) Conv3d (ABI 38) -- replaces nn.Conv3d(groups=num_groups) at resnet_helper.py:346-358 (BottleneckTransform.b
+ * of the ResNeXt configurations, RESNET.NUM_GROUPS > 1) and its autograd backward.  The descriptor is read as: Ci == Co == C, the
+ * channel count of the activation on both sides; Cw == Cg = C / groups, the channels per group of the fp32 weight
+ * [C][Cg][1][3][3]; Cow 0.  Supported: kernel (1,3,3), stride (1,1,1) or (1,2,2), dilation (1,k,k) with padding (0,k,k) for k = 1, 2,
+ * Cg in {4, 8, 16, 32, 64}, C a multiple of the bundle width B = max(32, Cg).  Anything else fails with a message that names what
+ * was asked for, and writes nothing.  A bundle is a run of B consecutive channels; its packed weight is the dense [B][9*B]
+ * operand with zeros off the diagonal blocks, and the bundle index is a grid dimension of the implicit-GEMM kernel.
+ * sf_gconv_prep_weights: wf[C][9*B] (row co, column tap*B + ci - bundle base) and, optionally, the data-gradient operand
+ *   wd[C][9*B] (row ci, column (8 - tap)*B + co - bundle base: transposed within each block, taps mirrored).  Every element of both
+ *   is written by the kernel.
+ * sf_gconv_fwd: y = act(conv(x) + bias), act = ReLU when out_relu (the eval form with BatchNorm folded in); bias [C] fp32 or NULL;
+ *   stat_part (optional) as sf_conv_fwd writes it: [sf_conv_fwd_mtiles(d)][2][C], sums of the fp32 accumulators.
+ * sf_gconv_dgrad: dx = conv_transpose(dy, w), dx pitch d->ldx, dy pitch d->ldy.
+ * sf_gconv_wgrad: dw[C][Cg][9] = (zero_first ? 0 : dw) + out_scale * dL/dw.  Per bundle the B x 9B product is formed in
+ *   `workspace` (>= sf_gconv_wgrad_workspace(d) bytes) and only its diagonal blocks are summed, in a fixed order (no atomics:
+ *   run-to-run identical), and stored. */
+int sf_gconv_prep_weights(const sf_conv_desc* d, const float* w, void* wf, void* wd, sf_stream_t stream);
+int sf_gconv_fwd(const sf_conv_desc* d, const void* x, const void* wf, const float* bias, int out_relu, void* y,
+                 float* stat_part, sf_stream_t stream);
+int sf_gconv_dgrad(const sf_conv_desc* d, const void* dy, const void* wd, void* dx, sf_stream_t stream);
+int64_t sf_gconv_wgrad_workspace(const sf_conv_desc* d);
+int sf_gconv_wgrad(const sf_conv_desc* d, const void* x, const void* dy, float* dw, float out_scale, int zero_first,
+                   void* workspace, int64_t workspace_bytes, sf_stream_t stream);
 /* Block-final BatchNorm backward fused into both gradients of the block's last convolution (ABI 32; resnet_helper.py:361-369,
  * :512-521).  Replaces the three calls sf_bn_bwd_apply(dz, mask_bits, yc, coef) -> dy_c, sf_conv_wgrad(act, dy_c) and
  * sf_conv_dgrad_bn(dy_c, wd) for a 1x1x1 unit-stride unpadded convolution d: dy_c = (f16)(k1 * g + k2 + k3 * yc) is formed per row

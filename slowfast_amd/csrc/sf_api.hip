@@ -4,6 +4,7 @@
 #include "sf_common.h"
 #include "sf_igemm.h"
 #include "sf_igemm2.h"
+#include "sf_gconv.h"
 #include "sf_wgrad2.h"
 #include "sf_cbwd.h"
 #include "sf_pool.h"
@@ -913,40 +914,33 @@ extern "C" int64_t sf_conv_wgrad_workspace(const sf_conv_desc* d) {
     return plain > affine ? plain : affine;
 }
 
-extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* in_scale, const float* in_shift,
-                             int in_relu, const void* dy, float* dw, float out_scale, int zero_first,
-                             void* workspace, int64_t workspace_bytes, const void* rowtab, sf_stream_t stream) {
-    if (check_desc(d)) return -1;
-    REQUIRE(x && dy && dw && workspace, "sf_conv_wgrad: null pointer");
-    REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "sf_conv_wgrad: in_scale/in_shift must come together");
-    REQUIRE(!in_scale || d->Ci <= 512, "sf_conv_wgrad: fused input BatchNorm supports Ci <= 512 (got %d)", d->Ci);
-    hipStream_t s = (hipStream_t)stream;
-    GatherSide gk = gather_fwd(d, x, in_scale, in_shift, in_relu);
-    const WgradPlan w = plan_conv_wgrad(d, in_scale != nullptr);
-    REQUIRE(workspace_bytes >= (int64_t)w.ws_bytes, "sf_conv_wgrad: workspace too small (%lld < %lld bytes)",
-            (long long)workspace_bytes, (long long)w.ws_bytes);
-    float* slabs = (float*)((char*)workspace + w.tab_bytes);
+// The partial tile sets of a planned weight gradient: `slabs` receives w.slabs sets of [Co_pad][Kpad] floats; `tab` is the row
+// table of the WGRAD_ROWTAB kernels (already built), `workspace` the head of the caller's workspace (WGRAD_STEM writes there).
+// `bundles` > 0 (sf_gconv_wgrad): d is the geometry of ONE bundle of d->Ci channels, x / dy / slabs those of bundle 0; the BUNDLED
+// kernels take bundle blockIdx.y from the same rows, d->Ci channels and one slab set further on.
+static void launch_wgrad_partials(const sf_conv_desc* d, const WgradPlan& w, const GatherSide& gk, const void* x, const void* dy,
+                                  float* slabs, const void* tab, void* workspace, hipStream_t s, int bundles = 0) {
     if (w.path == WGRAD_ROWTAB) {
-        REQUIRE(((uintptr_t)x | (uintptr_t)dy | (uintptr_t)workspace) % 16 == 0, "sf_conv_wgrad: operands must be 16-byte aligned");
         Wgrad2Params q;
         memset(&q, 0, sizeof(q));
         int ti = 0;
         for (int kt = 0; kt < d->kT; ++kt)
             for (int kh = 0; kh < d->kH; ++kh)
                 for (int kw = 0; kw < d->kW; ++kw, ++ti) q.dlin[ti] = (kt * d->dT * d->Hi + kh * d->dH) * d->Wi + kw * d->dW;
-        if (!rowtab) launch_rowtab(d, workspace, s);     // the caller keeps no table for this geometry: build it per call
-        else REQUIRE((uintptr_t)rowtab % 16 == 0, "sf_conv_wgrad: rowtab must be 16-byte aligned");
         q.x = (const f16*)x; q.ldx = d->ldx; q.C = d->Ci;
         q.dy = (const f16*)dy; q.ldy = d->ldy; q.Co = d->Co;
         q.M = d->N * d->To * d->Ho * d->Wo; q.Ktot = gk.Ktot;
-        q.rowtab = (const i32x2*)(rowtab ? rowtab : workspace);
+        q.rowtab = (const i32x2*)tab;
         q.ws = slabs; q.Co_pad = w.Co_pad; q.Kpad = w.Kpad;
         q.tiles_k = w.tiles_k; q.tiles_c = w.tiles_c; q.rows_per_split = w.rows_per_split;
         q.stage_stride = (w.thin && tune_knob("SF_WGRAD2T_RR", 1) != 0) ? w.splits : 0;
-        const dim3 grid((unsigned)(w.tiles_k * w.tiles_c * w.slabs));
+        const dim3 grid((unsigned)(w.tiles_k * w.tiles_c * w.slabs), bundles > 0 ? (unsigned)bundles : 1u);
         if (sf_trace()) fprintf(stderr, "[sfamd] wgrad2: M=%d Co=%d K=%d tiles %dx%d splits %d%s\n", q.M, q.Co, q.Ktot, w.tiles_c, w.tiles_k, w.splits,
                                 w.dual ? " (two per workgroup)" : "");
-        if (w.thin) {
+        if (bundles > 0) {          // 32- and 64-channel bundles: the thin 32 x 128 tile, the 64-row tile with one split per workgroup
+            if (w.thin) hipLaunchKernelGGL((sf_wgrad2t_kernel<32, 128, 2, true>), grid, dim3(256), 0, s, q);
+            else hipLaunchKernelGGL((sf_wgrad2_kernel<64, false, true>), grid, dim3(512), 0, s, q);
+        } else if (w.thin) {
             if (w.BMW == 16 && w.BKW == 128) hipLaunchKernelGGL((sf_wgrad2t_kernel<16, 128, 2>), grid, dim3(256), 0, s, q);
             else if (w.BMW == 32 && w.BKW == 128) hipLaunchKernelGGL((sf_wgrad2t_kernel<32, 128, 2>), grid, dim3(256), 0, s, q);
             else if (w.BMW == 16) hipLaunchKernelGGL((sf_wgrad2t_kernel<16, 32, 3>), grid, dim3(256), 0, s, q);
@@ -971,19 +965,204 @@ extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* 
         else if (sp.small) hipLaunchKernelGGL((sf_stem_wgrad_kernel<16, SF_STEM_CHUNKS_SMALL>), grid, block, 0, s, q);
         else hipLaunchKernelGGL((sf_stem_wgrad_kernel<16, SF_STEM_CHUNKS>), grid, block, 0, s, q);
     } else {
-        REQUIRE(w.splits <= 65535, "sf_conv_wgrad: too many splits");
         WgradParams p;
         memset(&p, 0, sizeof(p));
         p.g = gk;
         p.dy = (const f16*)dy; p.ldy = d->ldy; p.Co = d->Co;
         p.M = d->N * d->To * d->Ho * d->Wo;
-        p.ws = (float*)workspace; p.Co_pad = w.Co_pad; p.Kpad = w.Kpad;
+        p.ws = slabs; p.Co_pad = w.Co_pad; p.Kpad = w.Kpad;
         p.nchunks = w.nchunks; p.chunks_per_split = w.chunks_per_split;
+        if (bundles > 0) {
+            p.tiles_k = w.tiles_k; p.tiles_c = w.tiles_c;
+            const dim3 grid((unsigned)(w.tiles_k * w.tiles_c * w.splits), (unsigned)bundles), block(SF_THREADS);
+            if (w.BMW == 64) hipLaunchKernelGGL((sf_wgrad_kernel<64, 32, 64, 1, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((sf_wgrad_kernel<32, 32, 32, 4, true>), grid, block, 0, s, p);
+            return;
+        }
         launch_wgrad1(w.BMW, p, dim3(w.tiles_k, w.tiles_c, w.splits), s);
     }
+}
+
+extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const void* x, const float* in_scale, const float* in_shift,
+                             int in_relu, const void* dy, float* dw, float out_scale, int zero_first,
+                             void* workspace, int64_t workspace_bytes, const void* rowtab, sf_stream_t stream) {
+    if (check_desc(d)) return -1;
+    REQUIRE(x && dy && dw && workspace, "sf_conv_wgrad: null pointer");
+    REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "sf_conv_wgrad: in_scale/in_shift must come together");
+    REQUIRE(!in_scale || d->Ci <= 512, "sf_conv_wgrad: fused input BatchNorm supports Ci <= 512 (got %d)", d->Ci);
+    hipStream_t s = (hipStream_t)stream;
+    GatherSide gk = gather_fwd(d, x, in_scale, in_shift, in_relu);
+    const WgradPlan w = plan_conv_wgrad(d, in_scale != nullptr);
+    REQUIRE(workspace_bytes >= (int64_t)w.ws_bytes, "sf_conv_wgrad: workspace too small (%lld < %lld bytes)",
+            (long long)workspace_bytes, (long long)w.ws_bytes);
+    float* slabs = (float*)((char*)workspace + w.tab_bytes);
+    if (w.path == WGRAD_ROWTAB) {
+        REQUIRE(((uintptr_t)x | (uintptr_t)dy | (uintptr_t)workspace) % 16 == 0, "sf_conv_wgrad: operands must be 16-byte aligned");
+        if (!rowtab) launch_rowtab(d, workspace, s);     // the caller keeps no table for this geometry: build it per call
+        else REQUIRE((uintptr_t)rowtab % 16 == 0, "sf_conv_wgrad: rowtab must be 16-byte aligned");
+    } else if (w.path == WGRAD_GEN1) {
+        REQUIRE(w.splits <= 65535, "sf_conv_wgrad: too many splits");
+    }
+    launch_wgrad_partials(d, w, gk, x, dy, slabs, rowtab ? rowtab : workspace, workspace, s);
     if (check_launch("wgrad")) return -1;
     launch_wgrad_reduce(d, slabs, w.slabs, w.Co_pad, w.Kpad, w.path == WGRAD_STEM && w.stem.thin3, dw, out_scale, zero_first, s);
     return check_launch("wgrad_reduce");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Grouped 1x3x3 convolution on block-diagonal tiles (sf_gconv.h; resnet_helper.py:346-358 with groups = num_groups).  d->Ci == d->Co
+// is the channel count C of the activation, d->Cw the channels per group Cg of the fp32 weight [C][Cg][1][3][3].
+static inline int gconv_bundle(const sf_conv_desc* d) { return d->Cw > 32 ? d->Cw : 32; }
+static int check_gconv(const char* who, const sf_conv_desc* d) {
+    if (check_desc(d)) return -1;
+    REQUIRE(d->kT == 1 && d->kH == 3 && d->kW == 3, "%s: kernel (%d,%d,%d) is not supported: grouped convolutions are (1,3,3)", who,
+            d->kT, d->kH, d->kW);
+    REQUIRE(d->Ci == d->Co && (d->Cow == 0 || d->Cow == d->Co), "%s: a grouped convolution maps C to C channels (Ci=%d Co=%d Cow=%d)",
+            who, d->Ci, d->Co, d->Cow);
+    const int Cg = d->Cw;
+    REQUIRE(Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32 || Cg == 64,
+            "%s: %d channels per group are not supported: Cg must be one of 4, 8, 16, 32, 64", who, Cg);
+    const int B = gconv_bundle(d);
+    REQUIRE(d->Ci % B == 0, "%s: C=%d with Cg=%d is not a whole number of %d-channel bundles", who, d->Ci, Cg, B);
+    REQUIRE(d->sT == 1 && d->sH == d->sW && (d->sH == 1 || d->sH == 2), "%s: stride (%d,%d,%d) is not supported: (1,1,1) or (1,2,2)",
+            who, d->sT, d->sH, d->sW);
+    REQUIRE(d->dT == 1 && d->dH == d->dW && (d->dH == 1 || d->dH == 2) && d->pT == 0 && d->pH == d->dH && d->pW == d->dW,
+            "%s: dilation (%d,%d,%d) / padding (%d,%d,%d) is not supported: dilation (1,k,k) with k = 1 or 2 and padding (0,k,k)", who,
+            d->dT, d->dH, d->dW, d->pT, d->pH, d->pW);
+    return 0;
+}
+// the descriptor of one bundle: the dense B -> B convolution on the pitched rows of the whole tensor
+static sf_conv_desc gconv_bundle_desc(const sf_conv_desc* d) {
+    sf_conv_desc b = *d;
+    b.Ci = b.Co = b.Cw = gconv_bundle(d);
+    b.Cow = 0;
+    return b;
+}
+// sf_igemm2_kernel<.., BUNDLED>: 256 x 32 x 32 tiles for the 32-wide bundles, 256 x 64 tiles for the 64-wide ones (64 deep when the
+// grid is at most ~one tile per CU: plan_gemm2_tile's rule).  The tap columns of the mirrored data-gradient operand: `mirror`.
+static void gconv_launch(Igemm2Params& q, const sf_conv_desc* d, bool mirror, hipStream_t s) {
+    const int B = gconv_bundle(d), nb = d->Ci / B;
+    q.bundle_w = B; q.stat_ld = d->Co;
+    if (mirror)
+        for (int t = 0; t < q.ntaps; ++t) q.taps[t].wcol = (9 - 1) * B - q.taps[t].wcol;
+    const int mtiles = cdiv(q.M, 256);
+    q.ntiles_n = 1;
+    const dim3 grid((unsigned)mtiles, (unsigned)nb), block(512);
+    if (sf_trace()) fprintf(stderr, "[sfamd] gconv igemm2: M=%d bundles %d x %d taps=%d omap=%d\n", q.M, nb, B, q.ntaps, q.omap);
+    if (B == 32) hipLaunchKernelGGL((sf_igemm2_kernel<256, 32, 4, 2, 32, 3, false, true>), grid, block, 0, s, q);
+    else if ((int64_t)mtiles * nb <= 320) hipLaunchKernelGGL((sf_igemm2_kernel<256, 64, 4, 2, 64, 3, false, true>), grid, block, 0, s, q);
+    else hipLaunchKernelGGL((sf_igemm2_kernel<256, 64, 4, 2, 32, 3, false, true>), grid, block, 0, s, q);
+}
+static int check_gconv_act(const char* who, const void* a, int ld, int C) {
+    REQUIRE(a && (uintptr_t)a % 16 == 0 && ld >= C && ld % 8 == 0, "%s: activations must be 16-byte aligned with a pitch % 8 == 0 >= C", who);
+    return 0;
+}
+
+extern "C" int sf_gconv_prep_weights(const sf_conv_desc* d, const float* w, void* wf, void* wd, sf_stream_t stream) {
+    if (check_gconv("sf_gconv_prep_weights", d)) return -1;
+    REQUIRE(w && wf, "sf_gconv_prep_weights: null pointer");
+    GconvPrepParams p;
+    memset(&p, 0, sizeof(p));
+    p.w = w; p.wf = (f16*)wf; p.wd = (f16*)wd; p.C = d->Co; p.Cg = d->Cw; p.B = gconv_bundle(d); p.taps = 9;
+    const int64_t total = (int64_t)p.C * p.taps * p.B * (wd ? 2 : 1);
+    int blocks = cdiv(total, SF_THREADS);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(sf_gconv_prep_kernel, dim3(blocks), dim3(SF_THREADS), 0, (hipStream_t)stream, p);
+    return check_launch("gconv_prep_weights");
+}
+
+extern "C" int sf_gconv_fwd(const sf_conv_desc* d, const void* x, const void* wf, const float* bias, int out_relu, void* y,
+                            float* stat_part, sf_stream_t stream) {
+    if (check_gconv("sf_gconv_fwd", d)) return -1;
+    REQUIRE(wf && (uintptr_t)wf % 16 == 0, "sf_gconv_fwd: the packed weight must be 16-byte aligned");
+    if (check_gconv_act("sf_gconv_fwd", x, d->ldx, d->Ci) || check_gconv_act("sf_gconv_fwd", y, d->ldy, d->Co)) return -1;
+    const sf_conv_desc b = gconv_bundle_desc(d);
+    IgemmParams p = gemm_params(gather_fwd(&b, x, nullptr, nullptr, 0), d->N * d->To * d->Ho * d->Wo, wf, 9 * b.Ci, b.Co, y, d->ldy,
+                                bias, nullptr, 0);
+    p.stat_part = stat_part;
+    p.act_mode = out_relu ? 3 : 0;
+    Igemm2Params q;
+    igemm2_dense(q, p);
+    gconv_launch(q, d, false, (hipStream_t)stream);
+    return check_launch("gconv_fwd");
+}
+
+extern "C" int sf_gconv_dgrad(const sf_conv_desc* d, const void* dy, const void* wd, void* dx, sf_stream_t stream) {
+    if (check_gconv("sf_gconv_dgrad", d)) return -1;
+    REQUIRE(wd && (uintptr_t)wd % 16 == 0, "sf_gconv_dgrad: the packed weight must be 16-byte aligned");
+    if (check_gconv_act("sf_gconv_dgrad", dy, d->ldy, d->Co) || check_gconv_act("sf_gconv_dgrad", dx, d->ldx, d->Ci)) return -1;
+    const sf_conv_desc b = gconv_bundle_desc(d);
+    IgemmParams p = gemm_params(gather_dgrad(&b, dy), d->N * d->Ti * d->Hi * d->Wi, wd, 9 * b.Co, b.Ci, dx, d->ldx, nullptr, nullptr, 0);
+    Igemm2Params q;
+    if (d->sH == 1) {
+        igemm2_dense(q, p);
+        gconv_launch(q, d, true, (hipStream_t)stream);
+    } else {            // one launch per stride-residue class of input positions (igemm2_class), every bundle in each
+        for (int rh = 0; rh < d->sH; ++rh)
+            for (int rw = 0; rw < d->sW; ++rw) {
+                const int r[3] = {0, rh, rw};
+                if (!igemm2_class(q, p, r)) continue;
+                gconv_launch(q, d, true, (hipStream_t)stream);
+            }
+    }
+    return check_launch("gconv_dgrad");
+}
+
+// The bundles share ONE grid (blockIdx.y of the BUNDLED weight-gradient kernels): the dense planner picks the path and the tiles for
+// the B -> B geometry of a bundle, and each bundle takes 1 / nb of the splits that plan gives a whole layer -- together they fill
+// the chip once, as one dense layer does.  One split per workgroup (the pair kernel is not used).  Workspace: the row table, then
+// nb sets of `slabs` partial tiles.
+static WgradPlan plan_gconv_wgrad(const sf_conv_desc* b, int nb) {
+    WgradPlan w = plan_conv_wgrad(b, false);
+    const int64_t M = (int64_t)b->N * b->To * b->Ho * b->Wo;
+    int splits = w.splits / nb;
+    if (splits < 1) splits = 1;
+    if (w.path == WGRAD_ROWTAB) {
+        w.dual = false;
+        w.rows_per_split = roundup(cdiv(M, splits), w.thin ? 128 : 32);
+        w.splits = cdiv(M, w.rows_per_split);
+    } else if (w.path == WGRAD_GEN1) {
+        const int nstages = cdiv(w.nchunks, w.KS);
+        if (splits > nstages) splits = nstages;
+        w.chunks_per_split = cdiv(nstages, splits) * w.KS;
+        w.splits = cdiv(w.nchunks, w.chunks_per_split);
+    }
+    w.slabs = w.splits;
+    w.ws_bytes = w.tab_bytes + (size_t)nb * w.slabs * w.Co_pad * w.Kpad * 4;
+    return w;
+}
+
+extern "C" int64_t sf_gconv_wgrad_workspace(const sf_conv_desc* d) {
+    if (check_gconv("sf_gconv_wgrad_workspace", d)) return -1;
+    const sf_conv_desc b = gconv_bundle_desc(d);
+    return (int64_t)plan_gconv_wgrad(&b, d->Ci / b.Ci).ws_bytes;
+}
+
+extern "C" int sf_gconv_wgrad(const sf_conv_desc* d, const void* x, const void* dy, float* dw, float out_scale, int zero_first,
+                              void* workspace, int64_t workspace_bytes, sf_stream_t stream) {
+    if (check_gconv("sf_gconv_wgrad", d)) return -1;
+    REQUIRE(dw && workspace && (uintptr_t)workspace % 16 == 0, "sf_gconv_wgrad: null or unaligned pointer");
+    if (check_gconv_act("sf_gconv_wgrad", x, d->ldx, d->Ci) || check_gconv_act("sf_gconv_wgrad", dy, d->ldy, d->Co)) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const sf_conv_desc b = gconv_bundle_desc(d);
+    const int B = b.Ci, nb = d->Ci / B, Cg = d->Cw;
+    const WgradPlan w = plan_gconv_wgrad(&b, nb);
+    REQUIRE(w.path != WGRAD_STEM && w.BMW == B && (w.path != WGRAD_ROWTAB || !w.thin || w.BKW == 128), "sf_gconv_wgrad: unexpected plan");
+    REQUIRE(workspace_bytes >= (int64_t)w.ws_bytes, "sf_gconv_wgrad: workspace too small (%lld < %lld bytes)",
+            (long long)workspace_bytes, (long long)w.ws_bytes);
+    REQUIRE(nb <= 65535, "sf_gconv_wgrad: too many bundles");
+    float* slabs = (float*)((char*)workspace + w.tab_bytes);
+    if (w.path == WGRAD_ROWTAB) launch_rowtab(&b, workspace, s);
+    const GatherSide gk = gather_fwd(&b, x, nullptr, nullptr, 0);
+    launch_wgrad_partials(&b, w, gk, x, dy, slabs, workspace, workspace, s, nb);
+    if (check_launch("gconv_wgrad")) return -1;
+    GconvReduceParams r;
+    memset(&r, 0, sizeof(r));
+    r.ws = slabs; r.slabs = w.slabs; r.Co_pad = w.Co_pad; r.Kpad = w.Kpad; r.bundle_ws = (int64_t)w.slabs * w.Co_pad * w.Kpad;
+    r.dw = dw; r.C = d->Co; r.Cg = Cg; r.B = B; r.taps = 9;
+    r.out_scale = out_scale; r.accumulate = zero_first ? 0 : 1;
+    hipLaunchKernelGGL(sf_gconv_wgrad_reduce_kernel, dim3(cdiv((int64_t)d->Co * Cg * 9, SF_THREADS)), dim3(SF_THREADS), 0, s, r);
+    return check_launch("gconv_wgrad_reduce");
 }
 
 // ------------------------------------------------------------------------------------------------

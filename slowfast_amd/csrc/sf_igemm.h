@@ -578,7 +578,7 @@ __device__ __forceinline__ bool gather_offset_tap(const GatherSide& g, const Row
 //   KS  > 1: small-Co tiles are HBM-bound and latency-limited -- a long stage (128 positions) amortises the
 //            barrier and the load latency, one LDS buffer + register staging keeps 3 workgroups per CU.
 // MFMA fragments come from ds_read_b64_tr_b16 (hardware transpose read).
-template <int BMW, int WM, int WN, int KS>
+template <int BMW, int WM, int WN, int KS, bool BUNDLED = false>
 __global__ __launch_bounds__(SF_THREADS) void sf_wgrad_kernel(WgradParams p) {
     constexpr int BNW = 128, BKM = 32, ROWS = BKM * KS;
     constexpr int WAVES_N = BNW / WN, WAVES_M = BMW / WM;
@@ -614,6 +614,13 @@ __global__ __launch_bounds__(SF_THREADS) void sf_wgrad_kernel(WgradParams p) {
     const f16* x_src = g.src;
     const f16* dy_src = p.dy;
     f16* out16 = p.out16;
+    float* wsb = nullptr;
+    if constexpr (BUNDLED) {
+        // sf_gconv.h: blockIdx.y selects a bundle, a run of C == Co channels of the input and of dy, and the bundle's own slab set
+        x_src += (int)blockIdx.y * g.C;
+        dy_src += (int)blockIdx.y * g.C;
+        wsb = p.ws + (int64_t)blockIdx.y * (int64_t)(gridDim.x / (uint32_t)(p.tiles_k * p.tiles_c)) * p.Co_pad * p.Kpad;
+    }
     const int nstages = (p.nchunks + KS - 1) / KS;
     // this split's stages (chunks_per_split counts 32-position chunks and is a multiple of KS)
     int sb = bz * (p.chunks_per_split / KS);
@@ -744,7 +751,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_wgrad_kernel(WgradParams p) {
         return;
     }
     // every split owns its slab: plain (non-atomic) stores, also when it had no rows to reduce (zeros)
-    float* slab = p.ws + (int64_t)bz * p.Co_pad * p.Kpad;
+    float* slab = (BUNDLED ? wsb : p.ws) + (int64_t)bz * p.Co_pad * p.Kpad;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int kcol = n0 + wn * WN + j * 16 + pl;

@@ -70,6 +70,10 @@ struct Igemm2Params {
     int ablate;
     F32Rows f32;        // fp32 side rows of the output (token residual sums; sf_common.h), f32.out == nullptr: off
     int linear;         // host-side hint: a plain matrix product (tile choice, sf_api.hip)
+    // BUNDLED kernels only (sf_gconv.h: grouped convolutions on block-diagonal tiles): blockIdx.y selects a run of bundle_w channels;
+    // it offsets the channel base of src / y / bias / stat_part and the row base of wmat, C == Nout == bundle_w, and the statistics
+    // rows keep the pitch of the whole tensor (stat_ld columns).  No residual, side rows or fused reductions in that form.
+    int bundle_w, stat_ld;
 };
 
 // LDS operand tile [rows][BK] fp16; the 16-byte K slot of a row is XOR-swizzled so that the 16 lanes one ds_read_b128 phase
@@ -84,7 +88,7 @@ __device__ __forceinline__ int i2_lds_off(int row, int kslot) {
 // partial statistics from the accumulators, the tile staged through LDS (the operand stages are dead by now; the caller has
 // passed the workgroup barrier that ends its K loop) and stored in 16-byte row-contiguous pieces with residual (+ bit mask), GELU
 // epilogues, the fused BatchNorm-backward reduction.  acc[i][j] = rows wm * WM + i * 16 .., columns wn * WN + j * 16 .. of the tile.
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool F32R>
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool F32R, bool BUNDLED = false>
 __device__ __forceinline__ void i2_epilogue(const Igemm2Params& p, f32x4 (&acc)[BM / WAVES_M / 16][BN / WAVES_N / 16], f16* smem,
                                             float (*s_red)[2][BN], int* s_orow, int mt, int nt) {
     constexpr int NW = WAVES_M * WAVES_N, NT = 64 * NW;
@@ -97,13 +101,15 @@ __device__ __forceinline__ void i2_epilogue(const Igemm2Params& p, f32x4 (&acc)[
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int m0 = mt * BM, n0 = nt * BN;
+    int cb = 0, sld = p.Nout;                   // channel base of the bundle, pitch of a statistics row
+    if constexpr (BUNDLED) { cb = (int)blockIdx.y * p.bundle_w; sld = p.stat_ld; }
     // ---------------- epilogue: scale, bias, BatchNorm partial statistics (fp32, from the accumulators)
     {
         const float alpha = p.alpha != 0.f ? p.alpha : 1.f;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int colj = n0 + wn * WN + j * 16 + (lane & 15);
-            const float b = (p.bias && colj < p.Nout) ? p.bias[colj] : 0.f;
+            const float b = (p.bias && colj < p.Nout) ? p.bias[cb + colj] : 0.f;
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -156,8 +162,8 @@ __device__ __forceinline__ void i2_epilogue(const Igemm2Params& p, f32x4 (&acc)[
                 s += s_red[half * WPH + w][0][c];
                 q += s_red[half * WPH + w][1][c];
             }
-            p.stat_part[((int64_t)prow * 2 + 0) * p.Nout + col] = s;
-            p.stat_part[((int64_t)prow * 2 + 1) * p.Nout + col] = q;
+            p.stat_part[((int64_t)prow * 2 + 0) * sld + cb + col] = s;
+            p.stat_part[((int64_t)prow * 2 + 1) * sld + cb + col] = q;
         }
     }
     constexpr int CG = BN / 8;
@@ -220,7 +226,7 @@ __device__ __forceinline__ void i2_epilogue(const Igemm2Params& p, f32x4 (&acc)[
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = v[e] > (f16)0.f ? v[e] : (f16)0.f;
             }
-            st16(p.y + (int64_t)m * p.ldy + ecol, v);
+            st16(p.y + (int64_t)m * p.ldy + cb + ecol, v);
             if (p.act_mode == 1) {
                 f16x8 a;
 #pragma unroll
@@ -244,7 +250,7 @@ __device__ __forceinline__ void i2_epilogue(const Igemm2Params& p, f32x4 (&acc)[
 //  * issuing the next stage's copies between the two MFMA halves of a stage in half of the waves: a wash
 //    (profiles/r3/r3_v7_stagger_ab.txt).  profiles/r3/r3_v6_igemm2_ablation.md shows what bounds the loop instead: the copy stream
 //    alone and the MFMA stream alone each take 75-80 % of the kernel's time and overlap only partly.
-template <int BM, int BN, int WAVES_M, int WAVES_N, int BK, int NST, bool F32R = false>   // F32R: see sf_igemm_kernel
+template <int BM, int BN, int WAVES_M, int WAVES_N, int BK, int NST, bool F32R = false, bool BUNDLED = false>   // F32R: see sf_igemm_kernel; BUNDLED: Igemm2Params::bundle_w
 // register cap: the 32-deep variant must fit TWO workgroups per CU (4 waves per SIMD -> 128 VGPRs), the 64-deep one runs alone
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (BK == 32 ? 2 : 1) * (WAVES_M * WAVES_N) / 4) void sf_igemm2_kernel(Igemm2Params p) {
     constexpr int NW = WAVES_M * WAVES_N, NT = 64 * NW;
@@ -277,6 +283,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (BK == 32 ? 2 : 1) * (WAVES
     const int tile = (int)xcd_remap(blockIdx.x, gridDim.x);
     const int nt = tile % p.ntiles_n, mt = tile / p.ntiles_n;
     const int m0 = mt * BM, n0 = nt * BN;
+    const f16* src = p.src;
+    const f16* wmat = p.wmat;
+    if constexpr (BUNDLED) {
+        src += (int)blockIdx.y * p.bundle_w;
+        wmat += (int64_t)blockIdx.y * p.bundle_w * p.ldw;
+    }
 
     // ---- loader state: the rows this lane copies in every stage (instruction j of the wave -> rows (wave + NW*j)*RPI ..)
     const int lrow = lane / KSL;                                    // row inside a copy instruction
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (BK == 32 ? 2 : 1) * (WAVES
     for (int j = 0; j < NB; ++j) {
         int co = n0 + (wave + NW * j) * RPI + lrow;
         if (co >= p.Nout) co = p.Nout - 1;
-        bptr[j] = p.wmat + (int64_t)co * p.ldw + kslot * 8;
+        bptr[j] = wmat + (int64_t)co * p.ldw + kslot * 8;
     }
     const f16* const zline = reinterpret_cast<const f16*>(sf_zero_line);
     const int csteps = p.C / BK;                                    // K steps per tap
@@ -333,7 +345,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (BK == 32 ? 2 : 1) * (WAVES
         const int wk = p.taps[tap].wcol + c0;
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
-            const f16* g = ((amask[j] >> tap) & 1u) ? p.src + (aoff[j] + dsrc) : zline;
+            const f16* g = ((amask[j] >> tap) & 1u) ? src + (aoff[j] + dsrc) : zline;
             SF_GLOBAL_LOAD_LDS16(g, As + (wave + NW * j) * 512);
         }
 #pragma unroll
@@ -402,5 +414,5 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (BK == 32 ? 2 : 1) * (WAVES
         if (SF_ABLATE(p) & 8) return;
     }
 
-    i2_epilogue<BM, BN, WAVES_M, WAVES_N, F32R>(p, acc, smem, s_red, s_orow, mt, nt);
+    i2_epilogue<BM, BN, WAVES_M, WAVES_N, F32R, BUNDLED>(p, acc, smem, s_red, s_orow, mt, nt);
 }

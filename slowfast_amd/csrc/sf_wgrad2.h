@@ -38,6 +38,8 @@ struct Wgrad2Params {
                                         // round robin, split z takes the 128-position stages z, z + S, z + 2S, ... (at any
                                         // moment the resident workgroups then stream through ONE contiguous region)
 };
+// BUNDLED kernels (sf_gconv.h: grouped convolutions): blockIdx.y selects a bundle, a run of C == Co channels of x and dy, and the
+// bundle's own slab set in ws -- the gridDim.x / (tiles_k * tiles_c) slabs of one bundle lie one after another.
 
 struct RowtabParams {
     i32x2* tab;
@@ -80,7 +82,7 @@ __device__ __forceinline__ int w2_swz(int m) { return (m & 3) | (((m >> 3) & 1) 
 // the loop are what they were (16 waves and 144 KB per CU either way); the fp32 split partials written here and re-read by
 // sf_wgrad_reduce_kernel are halved -- they were 1.5x the algorithmic bytes of the layer for three rounds
 // (profiles/pmc_traffic_SLOWFAST_8x8_R50.json).  own + other is commutative: both halves of the tile see the same sum order.
-template <int BMW, bool DUAL = false>
+template <int BMW, bool DUAL = false, bool BUNDLED = false>
 __global__ __launch_bounds__(DUAL ? 1024 : 512, 4) void sf_wgrad2_kernel(Wgrad2Params p) {
     constexpr int BKW = 256, ROWS = 32, NW = 8, NST = 3;
     constexpr int WAVES_C = BMW / 64, WAVES_K = NW / WAVES_C;
@@ -97,6 +99,15 @@ __global__ __launch_bounds__(DUAL ? 1024 : 512, 4) void sf_wgrad2_kernel(Wgrad2P
     const int half = DUAL ? wave_all >> 3 : 0, wave = wave_all & 7;
     f16* const smem = smem_all + half * (NST * STAGE);
     const int wc = wave / WAVES_K, wk = wave % WAVES_K;
+    // the bundle's operands; every use below reads p.x / p.dy / p.ws itself when !BUNDLED (the dense code is what it was)
+    const f16* xsrc = nullptr;
+    const f16* dysrc = nullptr;
+    float* wsb = nullptr;
+    if constexpr (BUNDLED) {
+        xsrc = p.x + (int)blockIdx.y * p.C;
+        dysrc = p.dy + (int)blockIdx.y * p.C;
+        wsb = p.ws + (int64_t)blockIdx.y * (int64_t)(gridDim.x / (uint32_t)(p.tiles_k * p.tiles_c)) * p.Co_pad * p.Kpad;
+    }
     const uint32_t wg = xcd_remap(blockIdx.x, gridDim.x);
     const int bx = (int)(wg % (uint32_t)p.tiles_k);
     const int by = (int)((wg / (uint32_t)p.tiles_k) % (uint32_t)p.tiles_c);
@@ -166,7 +177,7 @@ __global__ __launch_bounds__(DUAL ? 1024 : 512, 4) void sf_wgrad2_kernel(Wgrad2P
         f16* Xs = Ys + Y_ELEMS;
         if (ywave) {
             const int m = r0 + step * ROWS + ymrow;
-            const f16* g = (m < r1 && yok) ? p.dy + (int64_t)m * p.ldy + yco : zline;
+            const f16* g = (m < r1 && yok) ? (BUNDLED ? dysrc : p.dy) + (int64_t)m * p.ldy + yco : zline;
             SF_GLOBAL_LOAD_LDS16_ASM(g, Ys + wave * 512);
         }
 #pragma unroll
@@ -174,7 +185,7 @@ __global__ __launch_bounds__(DUAL ? 1024 : 512, 4) void sf_wgrad2_kernel(Wgrad2P
             const int pos = xrr ? e[j][1].x : e[j][0].x;
             const uint32_t mk = (uint32_t)(xrr ? e[j][1].y : e[j][0].y);
             const bool ok = (mk & xbit[j]) != 0u;
-            const f16* g = ok ? p.x + ((int64_t)pos * p.ldx + xcol[j]) : zline;
+            const f16* g = ok ? (BUNDLED ? xsrc : p.x) + ((int64_t)pos * p.ldx + xcol[j]) : zline;
             SF_GLOBAL_LOAD_LDS16_ASM(g, Xs + (wave + 8 * j) * 512);
         }
     };
@@ -274,7 +285,7 @@ __global__ __launch_bounds__(DUAL ? 1024 : 512, 4) void sf_wgrad2_kernel(Wgrad2P
     }
 
     // every split (pair) owns its slab: plain stores, also when it had no rows to reduce (zeros)
-    float* slab = p.ws + (int64_t)bz * p.Co_pad * p.Kpad;
+    float* slab = (BUNDLED ? wsb : p.ws) + (int64_t)bz * p.Co_pad * p.Kpad;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int kcol = k0 + wk * WN + j * 16 + pl;
@@ -325,7 +336,7 @@ __device__ __forceinline__ void w2t_slot(int prow, int pc, int& row, int& chunk)
     else { row = w2t_swap23(prow); chunk = pc; }
 }
 
-template <int BMW, int BKW, int NST>
+template <int BMW, int BKW, int NST, bool BUNDLED = false>
 __global__ __launch_bounds__(256) void sf_wgrad2t_kernel(Wgrad2Params p) {
     constexpr int ROWS = 128, NW = 4;
     constexpr int TMC = BMW / 16, TNK = BKW / 16;
@@ -339,6 +350,15 @@ __global__ __launch_bounds__(256) void sf_wgrad2t_kernel(Wgrad2Params p) {
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the bundle's operands; every use below reads p.x / p.dy / p.ws itself when !BUNDLED (the dense code is what it was)
+    const f16* xsrc = nullptr;
+    const f16* dysrc = nullptr;
+    float* wsb = nullptr;
+    if constexpr (BUNDLED) {
+        xsrc = p.x + (int)blockIdx.y * p.C;
+        dysrc = p.dy + (int)blockIdx.y * p.C;
+        wsb = p.ws + (int64_t)blockIdx.y * (int64_t)(gridDim.x / (uint32_t)(p.tiles_k * p.tiles_c)) * p.Co_pad * p.Kpad;
+    }
     const uint32_t wg = xcd_remap(blockIdx.x, gridDim.x);
     const int bx = (int)(wg % (uint32_t)p.tiles_k);
     const int bz = (int)(wg / (uint32_t)p.tiles_k);
@@ -416,13 +436,13 @@ __global__ __launch_bounds__(256) void sf_wgrad2t_kernel(Wgrad2Params p) {
 #pragma unroll
         for (int j = 0; j < YPW; ++j) {
             const int m = r0 + step * rstep + yrow[j];
-            const f16* g = (m < r1 && yco[j] < p.Co) ? p.dy + (int64_t)m * p.ldy + yco[j] : zline;
+            const f16* g = (m < r1 && yco[j] < p.Co) ? (BUNDLED ? dysrc : p.dy) + (int64_t)m * p.ldy + yco[j] : zline;
             SF_GLOBAL_LOAD_LDS16_ASM(g, Ys + (wave + NW * j) * 512);
         }
 #pragma unroll
         for (int j = 0; j < XPW; ++j) {
             const bool ok = (emk[j] & xbit[j]) != 0u;
-            const f16* g = ok ? p.x + ((int64_t)epos[j] * p.ldx + xcol[j]) : zline;
+            const f16* g = ok ? (BUNDLED ? xsrc : p.x) + ((int64_t)epos[j] * p.ldx + xcol[j]) : zline;
             SF_GLOBAL_LOAD_LDS16_ASM(g, Xs + (wave + NW * j) * 512);
         }
     };
@@ -492,7 +512,7 @@ __global__ __launch_bounds__(256) void sf_wgrad2t_kernel(Wgrad2Params p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) red[(((wave * TMC + i) * TNK + j) * 4 + r) * 64 + lane] = acc[i][j][r];
     __syncthreads();
-    float* slab = p.ws + (int64_t)bz * p.Co_pad * p.Kpad;
+    float* slab = (BUNDLED ? wsb : p.ws) + (int64_t)bz * p.Co_pad * p.Kpad;
     constexpr int TILE_ELEMS = TMC * TNK * 256;
     for (int e = tid; e < TILE_ELEMS; e += 256) {
         const float v = (red[e] + red[TILE_ELEMS + e]) + (red[2 * TILE_ELEMS + e] + red[3 * TILE_ELEMS + e]);

@@ -604,6 +604,93 @@ class ConvUnit:
         return ops.conv_fwd_fused(x, packed[0], geom, bias=packed[1], resid=resid, relu=relu, out=out)
 
 
+class GroupedConvUnit(ConvUnit):
+    """nn.Conv3d(C, C, (1,3,3), groups=G) (+ its BatchNorm): conv b of a ResNeXt bottleneck (RESNET.NUM_GROUPS > 1) on the
+    block-diagonal bundle kernels (ops.gconv_*, csrc/sf_gconv.h).  The interface ResBlockFn asks of a unit: forward, backward (with and
+    without ``bn_fuse``: the BatchNorm-backward reduction is not fused here, ``part`` is None and the engine keeps the separate
+    pass), bn_backward, params, fold, infer.  The weight is packed by a launch of its own, keyed on the weight's version like
+    ConvUnit.weights and repeated under FORCE_WEIGHT_PREP so that a captured step picks up the optimizer update; it stays out of
+    WeightPackPlan (it never appends itself to PACK_RECORD)."""
+
+    def __init__(self, conv, bn=None):
+        assert conv.padding_mode == "zeros" and conv.bias is None
+        assert bn is None or bn.momentum is not None, "cumulative-average BatchNorm is not supported"
+        check_grouped_conv(conv)
+        self.conv, self.bn = conv, bn
+        self._geoms = {}
+        self._wkey, self._w, self._planned = None, None, False
+
+    def geom(self, in_shape):
+        key = tuple(in_shape)
+        g = self._geoms.get(key)
+        if g is None:
+            c = self.conv
+            g = self._geoms[key] = ops.GroupedConvGeom(key, c.groups, c.kernel_size, c.stride, c.padding, c.dilation)
+        return g
+
+    def weights(self, geom, fresh=False):
+        w = self.conv.weight
+        key = (w.data_ptr(), w._version, w.device, PARAM_EPOCH)
+        if (fresh and FORCE_WEIGHT_PREP) or self._wkey != key:
+            self._w = ops.gconv_prep_weights(w.detach(), geom)
+            self._wkey = key
+        return self._w
+
+    def forward(self, x, in_affine, training):
+        assert in_affine is None, "the grouped kernels read a plain (already activated) input"
+        geom = self.geom(x.shape)
+        wf, _ = self.weights(geom, fresh=True)
+        bn = self.bn
+        if bn is None:
+            return ops.gconv_fwd(x, wf, geom, stats=False)[0], None
+        use_batch_stats = training or bn.running_mean is None
+        y, part = ops.gconv_fwd(x, wf, geom, stats=use_batch_stats)
+        return y, bn_statistics(bn, part, geom.out_rows, geom.Co, training)
+
+    def backward(self, x, in_affine, dy, need_dx, resid=None, resid_bits=None, bn_fuse=None):
+        assert in_affine is None and resid is None and resid_bits is None
+        geom = self.geom(x.shape)
+        w = self.conv.weight
+        if w.requires_grad:
+            dw, zero_first = _grad_dest(w)
+            ops.gconv_wgrad(x, dy, geom, dw, out_scale=1.0, zero_first=zero_first)
+        if not need_dx:
+            return None
+        _, wd = self.weights(geom)
+        dx = ops.gconv_dgrad(dy, wd, geom)
+        return (dx, None) if bn_fuse is not None else dx
+
+    def fused_c_geom(self, x):
+        return None
+
+    def fused_proj_geom(self, x):
+        return None
+
+    def infer(self, x, relu=False, resid=None, out=None):
+        assert resid is None
+        geom = self.geom(x.shape)
+        packed = self._fold_packed.get(geom.in_shape)
+        if packed is None:
+            wf, _ = ops.gconv_prep_weights(self._fold_w, geom, need_dgrad=False)
+            packed = self._fold_packed[geom.in_shape] = (wf, None if self._fold_b is None else self._fold_b.contiguous())
+        return ops.gconv_fwd(x, packed[0], geom, bias=packed[1], relu=relu, stats=False, out=out)[0]
+
+
+def check_grouped_conv(conv):
+    """What the bundle kernels are built for, checked where the model is built: NotImplementedError naming the cfg keys."""
+    C, G = conv.in_channels, conv.groups
+    cg = C // G
+    ok = (conv.in_channels == conv.out_channels and cg in ops.GCONV_CG and C % max(32, cg) == 0
+          and tuple(conv.kernel_size) == (1, 3, 3) and tuple(conv.stride) in ((1, 1, 1), (1, 2, 2))
+          and tuple(conv.dilation) in ((1, 1, 1), (1, 2, 2)) and tuple(conv.padding) == (0,) + tuple(conv.dilation[1:]))
+    if not ok:
+        raise NotImplementedError(
+            f"grouped convolution {C} -> {conv.out_channels} with groups={G} ({cg} channels per group), kernel {tuple(conv.kernel_size)}, "
+            f"stride {tuple(conv.stride)}, dilation {tuple(conv.dilation)}: RESNET.NUM_GROUPS / RESNET.WIDTH_PER_GROUP must give "
+            f"a (1,3,3) convolution with {ops.GCONV_CG} channels per group and an inner width that is a multiple of "
+            f"max(32, channels per group)")
+
+
 class StemConvUnit(ConvUnit):
     """Conv3d with <= 4 input channels (the RGB stems) as a W-pair-folded implicit GEMM.
 

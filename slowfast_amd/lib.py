@@ -11,7 +11,7 @@ import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 37
+ABI_VERSION = 38
 # 16-bit storage type of activations / packed weights / MFMA operands, fixed per PROCESS: SF_ACT_DTYPE=fp16 (default) loads
 # libsfamd.so, =bf16 loads libsfamd_bf16.so -- the same sources compiled with -DSF_ACT_BF16 (bfloat16 storage,
 # v_mfma_f32_16x16x32_bf16); both are what torch.cuda.amp.autocast admits on the reference side (tools/train_net.py:101-118).
@@ -99,6 +99,11 @@ _SIGNATURES = {
     "sf_conv_wgrad_rowtab_bytes": (c_int64, [POINTER(ConvDesc)]),
     "sf_conv_wgrad_rowtab": (c_int, [POINTER(ConvDesc), _P, _P]),
     "sf_conv_wgrad": (c_int, [POINTER(ConvDesc), _P, _F, _F, c_int, _P, _F, c_float, c_int, _P, c_int64, _P, _P]),
+    "sf_gconv_prep_weights": (c_int, [POINTER(ConvDesc), _F, _P, _P, _P]),
+    "sf_gconv_fwd": (c_int, [POINTER(ConvDesc), _P, _P, _F, c_int, _P, _F, _P]),
+    "sf_gconv_dgrad": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P]),
+    "sf_gconv_wgrad_workspace": (c_int64, [POINTER(ConvDesc)]),
+    "sf_gconv_wgrad": (c_int, [POINTER(ConvDesc), _P, _P, _F, c_float, c_int, _P, c_int64, _P]),
     "sf_conv_c_bwd_plan": (c_int, [POINTER(ConvDesc), c_int, c_int, POINTER(c_int32), POINTER(c_int64)]),
     "sf_conv_c_bwd": (c_int, [POINTER(ConvDesc), _P, c_int32, _P, _P, c_int32, _F, _P, _P, _F, _F, _P, c_int32, _F, c_int32,
                               POINTER(c_int32), _P, c_int32, _F, c_float, c_int, _P, c_int64, _P]),

@@ -349,6 +349,107 @@ def _wgrad_rowtab(geom, d, device):
 
 
 # ------------------------------------------------------------------------------------------------
+# Grouped (1,3,3) convolution on block-diagonal tiles (csrc/sf_gconv.h): BottleneckTransform.b with RESNET.NUM_GROUPS > 1
+GCONV_CG = (4, 8, 16, 32, 64)       # channels per group the bundle scheme is built for
+
+
+class GroupedConvGeom:
+    """Geometry of one nn.Conv3d(C, C, (1,3,3), groups=G) call on a given input shape: ``Cg = C // G`` channels per group, bundles of
+    ``B = max(32, Cg)`` consecutive channels, packed operands [C][9*B].  Built for any request; what the kernels do not support
+    is rejected by the launcher (SfError naming what was asked for)."""
+
+    def __init__(self, in_shape, groups, kernel=(1, 3, 3), stride=1, padding=(0, 1, 1), dilation=1):
+        self.N, self.Ci, self.Ti, self.Hi, self.Wi = in_shape
+        if groups < 1 or self.Ci % groups:
+            raise ValueError(f"in_channels ({self.Ci}) must be divisible by groups ({groups})")
+        self.groups, self.Co, self.Cow = groups, self.Ci, self.Ci
+        self.Cg = self.Cw = self.Ci // groups
+        self.B = max(32, self.Cg)
+        self.k, self.s, self.p, self.d = _triple(kernel), _triple(stride), _triple(padding), _triple(dilation)
+        self.To, self.Ho, self.Wo = [
+            (i + 2 * p - d * (k - 1) - 1) // s + 1
+            for i, k, s, p, d in zip((self.Ti, self.Hi, self.Wi), self.k, self.s, self.p, self.d)]
+        self.taps = self.k[0] * self.k[1] * self.k[2]
+        self.ldw = self.taps * self.B
+        self.ws_bytes = None
+
+    @property
+    def in_shape(self):
+        return (self.N, self.Ci, self.Ti, self.Hi, self.Wi)
+
+    @property
+    def out_shape(self):
+        return (self.N, self.Co, self.To, self.Ho, self.Wo)
+
+    @property
+    def out_rows(self):
+        return self.N * self.To * self.Ho * self.Wo
+
+    def work(self, reads_x=0, reads_y=0, writes_x=0, writes_y=0):
+        """Algorithmic work of one launch: the REAL grouped MACs (Cg inputs per output channel), not the block-diagonal ones."""
+        xe = self.N * self.Ci * self.Ti * self.Hi * self.Wi
+        ye = self.out_rows * self.Co
+        return dict(flops=2.0 * self.out_rows * self.Co * self.Cg * self.taps,
+                    bytes=2.0 * ((reads_x + writes_x) * xe + (reads_y + writes_y) * ye))
+
+    def desc(self, ldx, ldy):
+        return ConvDesc(self.N, self.Ci, self.Ti, self.Hi, self.Wi, self.Co, self.To, self.Ho, self.Wo,
+                        *self.k, *self.s, *self.p, *self.d, self.Cg, ldx, ldy, 0)
+
+
+def gconv_prep_weights(w, geom, need_dgrad=True):
+    """fp32 grouped Conv3d weight [C][Cg][1][3][3] -> block-diagonal fp16 operands (forward, data gradient), each [C][9*B]."""
+    assert w.dtype == torch.float32 and tuple(w.shape) == (geom.Co, geom.Cg) + geom.k, (w.shape, geom.Co, geom.Cg)
+    w = w.contiguous()
+    wf = torch.empty((geom.Co, geom.ldw), dtype=_f16, device=w.device)
+    wd = torch.empty((geom.Ci, geom.ldw), dtype=_f16, device=w.device) if need_dgrad else None
+    get_lib().call("sf_gconv_prep_weights", byref(geom.desc(geom.Ci, geom.Co)), w.data_ptr(), wf.data_ptr(), _ptr(wd), _stream(w),
+                   work=dict(bytes=4.0 * w.numel() + 2.0 * wf.numel() * (2 if need_dgrad else 1)))
+    return wf, wd
+
+
+def gconv_fwd(x, wf, geom, bias=None, relu=False, stats=True, out=None):
+    """y = relu?(conv3d(x, groups) + bias); returns (y, stat_part or None) -- stat_part in conv_fwd's layout [mtiles][2][C]."""
+    assert tuple(x.shape) == geom.in_shape, (x.shape, geom.in_shape)
+    y = cl_empty(geom.out_shape, x.device) if out is None else out
+    assert tuple(y.shape) == geom.out_shape
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == geom.Co
+    lib = get_lib()
+    d = geom.desc(cl_ld(x), cl_ld(y))
+    part = None
+    if stats:
+        part = torch.empty(((geom.out_rows + 127) // 128, 2, geom.Co), dtype=torch.float32, device=x.device)
+    lib.call("sf_gconv_fwd", byref(d), x.data_ptr(), wf.data_ptr(), _ptr(bias), int(bool(relu)), y.data_ptr(), _ptr(part),
+             _stream(x), work=geom.work(reads_x=1, writes_y=1))
+    return y, part
+
+
+def gconv_dgrad(dy, wd, geom, out=None):
+    """dx = conv_transpose3d(dy, w, groups)."""
+    assert tuple(dy.shape) == geom.out_shape
+    dx = cl_empty(geom.in_shape, dy.device) if out is None else out
+    assert tuple(dx.shape) == geom.in_shape
+    get_lib().call("sf_gconv_dgrad", byref(geom.desc(cl_ld(dx), cl_ld(dy))), dy.data_ptr(), wd.data_ptr(), dx.data_ptr(),
+                   _stream(dy), work=geom.work(reads_y=1, writes_x=1))
+    return dx
+
+
+def gconv_wgrad(x, dy, geom, dw, out_scale=1.0, zero_first=True):
+    """dw (+)= out_scale * d(loss)/d(weight); dw is an fp32 tensor shaped like the grouped Conv3d weight."""
+    assert tuple(x.shape) == geom.in_shape and tuple(dy.shape) == geom.out_shape
+    assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == geom.Co * geom.Cg * geom.taps
+    lib = get_lib()
+    d = geom.desc(cl_ld(x), cl_ld(dy))
+    if geom.ws_bytes is None:
+        geom.ws_bytes = lib.call("sf_gconv_wgrad_workspace", byref(d))
+    ws = _workspace(x.device, geom.ws_bytes)
+    lib.call("sf_gconv_wgrad", byref(d), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), float(out_scale), int(zero_first),
+             ws.data_ptr(), ws.numel(), _stream(x), work=geom.work(reads_x=1, reads_y=1))
+    return dw
+
+
+# ------------------------------------------------------------------------------------------------
 def bn_finalize(part, count, gamma, beta, running_mean, running_var, momentum, eps, training=True, C=None):
     """Per-tile sums -> (scale, shift, mean, rstd); updates running statistics in training mode.  ``C`` = channel
     count of the (zero padded) activation buffer when it exceeds the parameter length."""

@@ -4,16 +4,18 @@ the fully fused schedule of engine.ResBlockFn; ``BottleneckTransform`` on its ow
 three conv+BN units materialised."""
 import torch.nn as nn
 
-from .engine import ConvBNActFn, ConvUnit, ResBlockFn, as_cl, run_pathways
+from .engine import ConvBNActFn, ConvUnit, GroupedConvUnit, ResBlockFn, as_cl, run_pathways
 
 
 class BottleneckTransform(nn.Module):
-    """Tx1x1 -> 1x3x3 -> 1x1x1 bottleneck; children a, a_bn, a_relu, b, b_bn, b_relu, c, c_bn."""
+    """Tx1x1 -> 1x3x3 -> 1x1x1 bottleneck; children a, a_bn, a_relu, b, b_bn, b_relu, c, c_bn.  ``num_groups`` > 1 (ResNeXt,
+    RESNET.NUM_GROUPS): b is built with groups=num_groups as the reference builds it (resnet_helper.py:346-358; same weight shape,
+    same state_dict) and runs on the block-diagonal bundle kernels (engine.GroupedConvUnit); what those do not support is a
+    NotImplementedError here, when the model is built."""
 
     def __init__(self, dim_in, dim_out, temp_kernel_size, stride, dim_inner, num_groups, stride_1x1=False,
                  inplace_relu=True, eps=1e-5, bn_mmt=0.1, dilation=1, norm_module=nn.BatchNorm3d, block_idx=0):
         super().__init__()
-        assert num_groups == 1, "ResNeXt (grouped 1x3x3) is outside the SlowFast/C2D hot path built so far"
         self.temp_kernel_size = temp_kernel_size
         self._inplace_relu, self._eps, self._bn_mmt, self._stride_1x1 = inplace_relu, eps, bn_mmt, stride_1x1
         s_a, s_b = (stride, 1) if stride_1x1 else (1, stride)
@@ -30,7 +32,8 @@ class BottleneckTransform(nn.Module):
         self.c.final_conv = True
         self.c_bn = norm_module(num_features=dim_out, **bn)
         self.c_bn.transform_final_bn = True
-        self._a, self._b, self._c = ConvUnit(self.a, self.a_bn), ConvUnit(self.b, self.b_bn), ConvUnit(self.c, self.c_bn)
+        b_unit = ConvUnit if num_groups == 1 else GroupedConvUnit
+        self._a, self._b, self._c = ConvUnit(self.a, self.a_bn), b_unit(self.b, self.b_bn), ConvUnit(self.c, self.c_bn)
         self._chain = (self._a, self._b, self._c)
 
     def forward(self, x):
@@ -41,7 +44,9 @@ class BottleneckTransform(nn.Module):
 
 class BasicTransform(nn.Module):
     """Tx3x3 (stride) -> BN -> ReLU -> 1x3x3 (dilated) -> BN; children a, a_bn, a_relu, b, b_bn
-    (slowfast/models/resnet_helper.py:27-115; the ResNet-18/34 style block, RESNET.TRANS_FUNC "basic_transform")."""
+    (slowfast/models/resnet_helper.py:27-115; the ResNet-18/34 style block, RESNET.TRANS_FUNC "basic_transform").  ``num_groups`` is
+    accepted and ignored, as the reference's BasicTransform ignores it (resnet_helper.py:39-61: both convolutions are dense whatever
+    RESNET.NUM_GROUPS says)."""
 
     def __init__(self, dim_in, dim_out, temp_kernel_size, stride, dim_inner=None, num_groups=1, stride_1x1=None,
                  inplace_relu=True, eps=1e-5, bn_mmt=0.1, dilation=1, norm_module=nn.BatchNorm3d, block_idx=0):
